@@ -28,6 +28,10 @@ Rank 0 prints ONE JSON line: metric/value per the driver contract plus
   "secondary"    (default workload, N = 1) the other BASELINE GPU configs as complete lines of their own: nf4dq_ffn (configs[2]),
                  int8_4096 (configs[3]), nf4_m1 (configs[1] stand-alone), each with roofline, traffic and cpu_baseline
   "no_prewarm"   the same K steps timed before the disclosed time-based pre-warm (cold clock)
+
+--dump-outputs DIR writes what the last timed step returned (for every workload the line times) as DIR/<workload>.npy in
+float32, outputs above DUMP_MAX_ELEMS as a fixed, seeded sample of whole rows; the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -66,7 +70,39 @@ def parse():
     ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step loop; the median one is reported")
     ap.add_argument("--chunks", type=int, default=2, help="N>1: row chunks of the `chunked` curve (GEMM chunk i+1 under the gather of chunk i)")
     ap.add_argument("--verify", action="store_true", help="N>1: check gathered output == unsharded result on rank 0")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of each timed workload returned as DIR/<workload>.npy (float32); an output "
+                         "of more than %d elements is written as a fixed, seeded sample of whole rows (ascending row order)" % DUMP_MAX_ELEMS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_ELEMS = 3 << 20    # 12 MiB of float32 per dumped array: the four of the default line stay well under 64 MB
+
+
+def dump_sample(y, seed=0):
+    """A host float32 copy of one output (or of a list of outputs, stacked) for --dump-outputs.  Outputs of more than
+    DUMP_MAX_ELEMS elements keep a fixed, seeded choice of whole rows (the last dimension), in ascending order."""
+    if isinstance(y, (list, tuple)):
+        y = torch.stack([t.detach() for t in y])
+    rows = y.detach().reshape(-1, y.shape[-1])
+    if rows.numel() > DUMP_MAX_ELEMS:
+        keep = max(1, DUMP_MAX_ELEMS // rows.shape[1])
+        idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+        rows = rows[idx.to(rows.device)]
+        return rows.float().cpu().numpy()
+    return rows.reshape(y.shape).float().cpu().numpy()
+
+
+def write_dumps(path, dumps):
+    """DIR/<name>.npy for every array of `dumps`; returns {name: shape} for the bench line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in dumps.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in dumps.items()}
 
 
 def probe_lib():
@@ -124,7 +160,7 @@ def _outlier_traffic():
         return None
 
 
-def bench_nn(args, wl, dev, bnb, synthetic):
+def bench_nn(args, wl, dev, bnb, synthetic, dumps):
     """SURVEY 8f rank-3 rows on one GPU: 4-bit / 8-bit embedding lookups (HBM-bound gathers over a 32000 x 4096 table,
     8192 looked-up rows per step) and OutlierAwareLinear.forward (4096^3, 16 outlier columns, int8 MFMA)."""
     import numpy as np
@@ -155,10 +191,14 @@ def bench_nn(args, wl, dev, bnb, synthetic):
             step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        last = step()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dumps[wl] = dump_sample(last)
+        del last
         kern_ms = event_time_ms(step, args.steps)
         nbytes = bytes_per_row * tokens
         gbs = nbytes / (kern_ms * 1e-3) / 1e9
@@ -192,10 +232,14 @@ def bench_nn(args, wl, dev, bnb, synthetic):
             step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        last = step()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dumps[wl] = dump_sample(last)
+        del last
         kern_ms = event_time_ms(step, args.steps)
         flops = 2.0 * M * N * K
         tf = flops / (kern_ms * 1e-3) / 1e12
@@ -233,10 +277,14 @@ def bench_nn(args, wl, dev, bnb, synthetic):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dumps[wl] = dump_sample(last)
+    del last
     kern_ms = event_time_ms(step, args.steps)
     ops = 2.0 * M * N * K
     tops = ops / (kern_ms * 1e-3) / 1e12
@@ -362,6 +410,7 @@ class Timer:
 
     def __init__(self, distributed, dist, reduce_dev):
         self.distributed, self.dist, self.reduce_dev = distributed, dist, reduce_dev
+        self.last = None     # what the last step of the last run() returned (complete: read after its fence)
 
     def _fence(self):
         torch.cuda.synchronize()
@@ -385,12 +434,14 @@ class Timer:
         out = []
         st = torch.cuda.current_stream()
         for _ in range(reps):
+            self.last = None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             self._fence()
             t0 = time.perf_counter()
             e0.record(st)
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 step()
+            last = step()
             e1.record(st)
             if finish is not None:
                 finish()
@@ -402,6 +453,8 @@ class Timer:
                 self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
                 elapsed, ev_ms = float(t[0].item()), float(t[1].item())
             out.append((elapsed, ev_ms))
+            self.last = last
+            del last
         return out
 
 
@@ -459,8 +512,7 @@ def measure(args, wl, ctx):
             X = gen_normal(synthetic, (1, K), dt, 4321 + rank, 1.0, dev)
 
             def eager_pass():
-                for p, st in layers:
-                    bnb.matmul_4bit(X, p, st)
+                return [bnb.matmul_4bit(X, p, st) for p, st in layers]
             # one HIP graph of the 64 launches: the per-layer kernel (~5 us) is shorter than a Python-issued launch, so an
             # eager loop would time the host
             for _ in range(2):
@@ -472,9 +524,13 @@ def measure(args, wl, ctx):
             with torch.cuda.stream(side):
                 eager_pass()
                 with torch.cuda.graph(m1_graph, stream=side):
-                    eager_pass()
+                    m1_outs = eager_pass()     # the graph's output buffers: every replay rewrites them
             torch.cuda.current_stream().wait_stream(side)
-            modes["main"] = (m1_graph.replay, None)
+
+            def m1_step():
+                m1_graph.replay()
+                return m1_outs
+            modes["main"] = (m1_step, None)
             flops_per_step = 2.0 * N * K * 64
             bytes_per_launch = N * K // 2 + N * (K // 64) * 4 + K * 2 + N * 2   # 9 453 568 B
         else:
@@ -484,7 +540,7 @@ def measure(args, wl, ctx):
             X = gen_normal(synthetic, (e_row - s_row, K), dt, 4321 + rank, 1.0, dev)   # this rank's rows of the global batch
 
             def gemm_step():
-                bnb.matmul_4bit(X, packed, state)
+                return bnb.matmul_4bit(X, packed, state)
             flops_per_step = 2.0 * M * N * K
             if not do_gather:
                 modes["main"] = (gemm_step, None)
@@ -505,6 +561,7 @@ def measure(args, wl, ctx):
                     if pending[i] is not None:
                         pending[i][0].wait()
                     pending[i] = (dist.all_gather_into_tensor(gathered[i], y, async_op=True), y)
+                    return gathered[i]     # complete once overlapped_finish() has waited for its gather
 
                 def overlapped_finish():
                     for i in range(2):
@@ -515,6 +572,7 @@ def measure(args, wl, ctx):
                 def sync_step():
                     y = bnb.matmul_4bit(X, packed, state)
                     dist.all_gather_into_tensor(gathered[0], y)
+                    return gathered[0]
 
                 cg = ChunkedGather(lambda x: bnb.matmul_4bit(x, packed, state), e_row - s_row, N, dt, dev, world,
                                    chunks=args.chunks)
@@ -533,7 +591,7 @@ def measure(args, wl, ctx):
         del A16, B16, Bt
 
         def step():
-            bnb.matmul_int8(A, B, sa, sb, torch.float16)
+            return bnb.matmul_int8(A, B, sa, sb, torch.float16)
         modes["main"] = (step, None)
         flops_per_step = 2.0 * M * N * K
 
@@ -544,12 +602,16 @@ def measure(args, wl, ctx):
     if finish is not None:
         finish()
     cold = timer.run(step, finish, args.steps, 1)[0]
+    timer.last = None
     prewarm_steps = timer.prewarm(step, finish, args.prewarm_ms) if args.prewarm_ms > 0 else 0
     for _ in range(args.warmup):
         step()
     if finish is not None:
         finish()
     reps = timer.run(step, finish, args.steps, reps_n)
+    if args.dump_outputs and rank == 0:
+        ctx.dumps[wl] = dump_sample(timer.last.reshape(M_global, N) if do_gather else timer.last)
+    timer.last = None
     elapsed, ev_ms = median_rep(reps)
     kernel_name = _native.last_kernel()
     out["prewarm_ms"] = args.prewarm_ms
@@ -934,10 +996,15 @@ def main():
     wl = args.workload
     if wl in ("embed4", "embed8", "outlier", "w8a16", "fp8"):
         if rank == 0:
-            print(json.dumps(bench_nn(args, wl, dev, bnb, synthetic)))
+            dumps = {}
+            out = bench_nn(args, wl, dev, bnb, synthetic, dumps)
+            if args.dump_outputs:
+                out["dumped_outputs"] = write_dumps(args.dump_outputs, dumps)
+            print(json.dumps(out))
         return
     ctx = Ctx()
     ctx.world, ctx.rank, ctx.dev, ctx.dist, ctx.distributed, ctx.rehearse = world, rank, dev, dist, distributed, rehearse
+    ctx.dumps = {}
     out = measure(args, wl, ctx)
     if rank == 0 and world == 1 and wl == "nf4_m4096" and not args.no_secondary:
         # the other BASELINE GPU configs under the same clock: configs[2] (11008 x 4096 + double quant), configs[3] (int8 4096^3),
@@ -960,6 +1027,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            out["dumped_outputs"] = write_dumps(args.dump_outputs, ctx.dumps)
         out["digest"] = digest(out)      # LAST key: survives a record that keeps only the tail of the line
         print(json.dumps(out))
 

@@ -39,3 +39,44 @@ def test_world_size_mismatch_is_refused():
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 2
     assert "--gpus 4 but WORLD_SIZE=2" in p.stdout
+
+
+def test_steps_below_one_is_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
+def test_dump_sample_is_a_fixed_bounded_row_sample():
+    import bench
+    y = torch.randn(4096, 4096).to(torch.bfloat16)
+    a, b = bench.dump_sample(y), bench.dump_sample(y.clone())
+    assert a.dtype.name == "float32" and a.size <= bench.DUMP_MAX_ELEMS and a.shape[1] == 4096
+    assert (a == b).all()
+    # whole rows of the output, in ascending row order
+    rows = [int(torch.nonzero((y.float() == torch.from_numpy(r)).all(1))[0]) for r in a[:: len(a) // 8]]
+    assert rows == sorted(rows)
+    small = [torch.randn(1, 64) for _ in range(3)]
+    assert (bench.dump_sample(small) == torch.stack(small).numpy()).all()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the timed matmul_4bit returned, as the same call on the same seeded inputs computes it here."""
+    import numpy as np
+    import bench
+    import mps_bitsandbytes_amd as bnb
+    from mps_bitsandbytes_amd import synthetic
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reps", "1",
+                        "--prewarm-ms", "0", "--no-cpu-baseline", "--no-gemv", "--no-empirical", "--no-secondary",
+                        "--dump-outputs", str(tmp_path)], env=_env(), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["dumped_outputs"] == {"nf4_m4096": [768, 4096]}
+    got = np.load(tmp_path / "nf4_m4096.npy")
+    dev = torch.device("cuda")
+    W = synthetic.normal_device((4096, 4096), torch.bfloat16, seed=1234, std=1.0, device=dev)
+    packed, state = bnb.quantize_nf4(W, blocksize=64)
+    X = synthetic.normal_device((4096, 4096), torch.bfloat16, seed=4321, std=1.0, device=dev)
+    want = bench.dump_sample(bnb.matmul_4bit(X, packed, state))
+    assert got.dtype == np.float32 and np.array_equal(got, want)
