@@ -746,31 +746,19 @@ static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t 
         }
         const bool fast = (K % 16 == 0) && (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & 15) == 0) && M > 4;
         if (fast && (K % 64 == 0) && ((M + 255) / 256) * ((N + 255) / 256) >= 96) {
-            // large problems: the 256 x 256 one-workgroup-per-CU kernel with the int8 -> 16-bit decode in the
-            // weight-tile producer (gemm256.h, k_gemm256)
+            // large problems: the 256 x 256 one-workgroup-per-CU kernel on the LDS-DMA pipeline (gemm256w.h): activations
+            // and raw int8 weights by global_load_lds, the int8 -> 16-bit decode of I8ProducerRT (gemm256.h).
+            // W is 16-byte aligned here: `fast` requires it.
             using P = I8ProducerRT<T, WF>;
             typename P::Params wp{W, scales, N, K};
             const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
             const int od = std::is_same<T, f16_t>::value ? MBNB_F16 : MBNB_BF16;
-#ifdef MBNB_ABLATION
-            static const bool old_w8 = getenv("MBNB_W8_REGSTAGED") != nullptr;   // diagnostic builds only: register-staged k_gemm256
-#else
-            constexpr bool old_w8 = false;
-#endif
-            if (!old_w8 && ((reinterpret_cast<uintptr_t>(W) & 15) == 0)) {
-                // LDS-DMA pipeline (gemm256w.h): activations and raw int8 weights by global_load_lds
-                auto kw = k_gemm256w<T, WF>;
-                constexpr int ldsw = gemm256w_lds_bytes();
-                if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kw), ldsw, "linear_int8(mfma256w)")) return rc;
-                hipLaunchKernelGGL(kw, dim3((unsigned)tiles), dim3(512), ldsw, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
-                set_kernel_name(WF == W8_INT8 ? "w8a16_mfma256" : "fp8a16_mfma256");
-                return check_launch("linear_int8(mfma256w)");
-            }
-            auto kern = k_gemm256<T, P>;
-            if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), G256_LDS, "linear_int8(mfma256)")) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), G256_LDS, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
+            auto kw = k_gemm256w<T, WF>;
+            constexpr int ldsw = gemm256w_lds_bytes();
+            if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kw), ldsw, "linear_int8(mfma256w)")) return rc;
+            hipLaunchKernelGGL(kw, dim3((unsigned)tiles), dim3(512), ldsw, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
             set_kernel_name(WF == W8_INT8 ? "w8a16_mfma256" : "fp8a16_mfma256");
-            return check_launch("linear_int8(mfma256)");
+            return check_launch("linear_int8(mfma256w)");
         }
         if (fast) {
             using P = I8Producer<T, WF>;

@@ -11,7 +11,6 @@
 // Numerics follow the reference CPU branch (functional.py:752-773): the decoded weight is
 // rounded to the weight dtype before the contraction, accumulation is f32, one rounding of the
 // result to the weight dtype, then a cast to the requested output dtype.
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -275,15 +274,10 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
         // split-K needs the caller's workspace (mbnb_matmul_4bit_ws): full 128 x 128 f32 tiles per slice
         const bool splitk = fast_layout && slices > 1 && ws != nullptr && ((reinterpret_cast<uintptr_t>(ws) & 15) == 0) &&
                             ws_bytes >= slices * ((M + 127) / 128) * ((N + 127) / 128) * 65536;
-#ifdef MBNB_ABLATION
-        static const bool no_skinny = getenv("MBNB_NO_SKINNY") != nullptr;   // diagnostic builds only: A/B switch
-#else
-        constexpr bool no_skinny = false;
-#endif
         // weight-streaming regime with a few activation rows: 2 <= M <= 32, and up to 64 for layers of <= 16 Mi weights
         // (beyond that the activation re-reads of the skinny kernel cost more than split-K's second pass)
         const bool small_ok = blocksize >= 32 && gemm_small_shape(M, N, K, K_weight);   // 32 < M <= 256: gemm_small.h
-        const bool skinny = fast_layout && !no_skinny && M >= 2 && !small_ok && (M <= 32 || (M <= 64 && N * K <= ((int64_t)1 << 24))) &&
+        const bool skinny = fast_layout && M >= 2 && !small_ok && (M <= 32 || (M <= 64 && N * K <= ((int64_t)1 << 24))) &&
                             (K % 128 == 0);
         if (fast_layout && M <= 16 && (K % 32 == 0) && !(splitk && M > 4) && !skinny) {
             const int sh = ilog2(blocksize);
@@ -380,26 +374,11 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
             const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
             int od = sizeof(OutT) == 4 ? MBNB_F32 : (std::is_same<OutT, f16_t>::value ? MBNB_F16 : MBNB_BF16);
             if (bs2_pow2) {
-                using KernT = void (*)(const T *, typename P::Params, const T *, void *, int, int64_t, int64_t, int64_t);
-                // k_gemm256p with the byte-table decode; at blocksize 64 the absmax (plain f32, or int8 codes + absmax2)
-                // is fetched once per four k-steps (AM4).  Diagnostic builds (-DMBNB_ABLATION) read A/B switches for
-                // those two and for the schedule variants from the environment; the product reads no environment.
-#ifdef MBNB_ABLATION
-                static const bool no_blut = getenv("MBNB_NO_BLUT") != nullptr;
-                static const bool no_am4 = getenv("MBNB_NO_AM4") != nullptr;
-#else
-                constexpr bool no_blut = false, no_am4 = false;
-#endif
-                KernT kern = no_blut ? k_gemm256p<T, NESTED> : k_gemm256p<T, NESTED, 0, false, true>;
-                bool am4 = !no_am4 && blocksize == 64 && (K_weight % 256 == 0);
+                // k_gemm256p; at blocksize 64 the absmax (plain f32, or int8 codes + absmax2) is fetched once per
+                // four k-steps (AM4)
+                bool am4 = blocksize == 64 && (K_weight % 256 == 0);
                 if constexpr (NESTED) am4 = am4 && am.bs2 >= 4 && (reinterpret_cast<uintptr_t>(am.i8) & 3) == 0;
-                if (am4) kern = no_blut ? k_gemm256p<T, NESTED, 0, true> : k_gemm256p<T, NESTED, 0, true, true>;
-#ifdef MBNB_ABLATION
-                static const bool use_p = getenv("MBNB_256P") != nullptr;   // diagnostic builds: the round-1 kernel for every shape
-#else
-                constexpr bool use_p = false;
-#endif
-                if (am4 && !use_p) {
+                if (am4) {
                     // blocksize 64: k_gemm_fused4 (gemm_fused4.h: the decode inside the four-wave MFMA pipeline; the no-scratch kernel since
                     // round 4 -- 117.5 us against 120.3 for the eight-wave k_gemm256s at 4096^3, tools/exp/parked/); what it does not take
                     // (unaligned packed bytes / absmax) stays on k_gemm256p below
@@ -407,27 +386,7 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
                                                             bias, od, out, st);
                     if (rc4 != MBNB_NOT_APPLICABLE) return rc4;
                 }
-#ifdef MBNB_ABLATION
-                // diagnostic builds: the measured schedule alternatives
-                static const bool use_pp = getenv("MBNB_PINGPONG") != nullptr;    // ping-pong schedule
-                static const bool use_valu = getenv("MBNB_VALUDEC") != nullptr;   // slot-pinned + VALU decode
-                if (use_pp) kern = k_gemm256pp<T, NESTED>;
-                if (use_valu) kern = (!NESTED && am4) ? k_gemm256v<T, NESTED, 0, !NESTED> : k_gemm256v<T, NESTED>;
-#else
-                constexpr bool use_pp = false;
-#endif
-#ifdef MBNB_ABLATION
-                if constexpr (std::is_same<T, bf16_t>::value && !NESTED) {
-                    static const int abl = getenv("MBNB_ABLATE") ? atoi(getenv("MBNB_ABLATE")) : 0;
-                    switch (abl) {
-#define MBNB_ABL(v) case v: kern = use_pp ? k_gemm256pp<T, NESTED, v> : k_gemm256p<T, NESTED, v>; break;
-                        MBNB_ABL(1) MBNB_ABL(2) MBNB_ABL(3) MBNB_ABL(4) MBNB_ABL(8) MBNB_ABL(16) MBNB_ABL(12) MBNB_ABL(20)
-                        MBNB_ABL(24) MBNB_ABL(28) MBNB_ABL(31) MBNB_ABL(7) MBNB_ABL(23) MBNB_ABL(32) MBNB_ABL(64) MBNB_ABL(128) MBNB_ABL(256) MBNB_ABL(512) MBNB_ABL(520) MBNB_ABL(535) MBNB_ABL(1024) MBNB_ABL(2048) MBNB_ABL(2056) MBNB_ABL(4096) MBNB_ABL(4608) MBNB_ABL(516) MBNB_ABL(515) MBNB_ABL(528) MBNB_ABL(532) MBNB_ABL(519) MBNB_ABL(32768) MBNB_ABL(65536) MBNB_ABL(98304)
-#undef MBNB_ABL
-                        default: break;
-                    }
-                }
-#endif
+                auto kern = am4 ? k_gemm256p<T, NESTED, true> : k_gemm256p<T, NESTED, false>;
                 constexpr int lds = gemm256p_lds_bytes<NESTED>();
                 if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), lds, "matmul_4bit(mfma256)")) return rc;
                 hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
@@ -505,12 +464,6 @@ static int matmul4_out(const void *A, int64_t M, int64_t K, const uint8_t *packe
         default: return matmul4_qt<T, float>(A, M, K, packed, am, N, K_weight, blocksize, qt, bias, out, ws, ws_bytes, st);
     }
 }
-
-#ifdef MBNB_ABLATION
-extern "C" int mbnb_debug_read_stamps(unsigned long long *host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dbg_stamps), sizeof(unsigned long long) * 2 * 1024);
-}
-#endif
 
 int matmul_4bit_dispatch(const void *A, int64_t M, int64_t K, const uint8_t *packed, const AbsmaxView &am, int64_t N,
                          int64_t K_weight, int blocksize, int qt, int w_dtype, const void *bias, int out_dtype,

@@ -34,7 +34,7 @@ extern "C" int exp_gemm256(int variant, const void *X, const uint8_t *packed, co
     AbsmaxView am{absmax, nullptr, nullptr, 1};
     Q4ProducerRT<bf16_t, false>::Params wp{packed, am, N, K_weight, K_weight / 64, 6, MBNB_NF4, 0, 8, 6};
     if (variant < 0) {
-        auto kern = k_gemm256p<bf16_t, false, 0, true, true>;
+        auto kern = k_gemm256p<bf16_t, false, true>;
         constexpr int lds = gemm256p_lds_bytes<false>();
         static bool done = false;
         if (!done) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -2; done = true; }

@@ -17,7 +17,7 @@
 //   4  ADMA   LDS-DMA issued from inline assembly (gemm_tile.h lds_dma): the compiler's LDS waits become exact
 //             lgkmcnt(n) instead of lgkmcnt(0) after a "pending FLAT" access.
 //
-// Everything else is k_gemm256p<T, NESTED, 0, AM4 = true, BLUT = true>: same tile -> workgroup map, LDS images and swizzle,
+// Everything else is k_gemm256p<T, NESTED, AM4 = true>: same tile -> workgroup map, LDS images and swizzle,
 // byte-table decode (B operand = the bits dequantize_4bit produces), absmax-by-4 fetch, fragment double buffering, one
 // barrier per k-step between MFMA groups 2 and 3, LDS-staged epilogue.  Requirements (checked by the launcher):
 // blocksize 64, K % 64 == 0, K_weight % 256 == 0, 16-byte aligned X / packed rows, (NESTED: blocksize2 % 4 == 0 and a

@@ -1,5 +1,5 @@
 """Per-k-step time of the 4096x4096 NF4 GEMM for row strides K that are / are not powers of two
-(L2 channel hot-spotting probe).  Env switches (MBNB_ABLATE with an ablation build) are inherited."""
+(L2 channel hot-spotting probe)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mps_bitsandbytes_amd as bnb
