@@ -279,6 +279,39 @@ int mbnb_linear_fp8(const void *X, int dtype, int64_t M, int64_t K, const uint8_
                     int64_t N, const void *bias, void *out, void *workspace, int64_t workspace_bytes, int flags,
                     void *stream);
 
+/* ---------------------------------------------------------------------------
+ * linear_grad_input — the input gradient of every quantised linear above (the reference's CPU path is differentiable:
+ * matmul_4bit, Linear8bit.forward and matmul_fp8_e4m3 end in F.linear on the dequantised weight, functional.py:767, :806,
+ * nn/linear8bit.py:102), i.e. the forward's product in the other orientation:
+ *   dX[M,K] = cast_out( round_w( dY[M,N] · dequant(W)[N,K] ) )
+ * dY in `w_dtype`, f32 accumulation, one rounding to `w_dtype`, then the cast to `out_dtype`.
+ *   w_format  MBNB_NF4 / MBNB_FP4: W = packed u8 [N, K_weight/2], `absmax` as for mbnb_matmul_4bit, `blocksize`;
+ *             MBNB_W_INT8_ROWWISE: W = int8 [N, K], `scales` [N] (dequantize_rowwise: q * (scale / 127));
+ *             MBNB_W_FP8_E4M3: W = u8 [N, K] in the reference's FP8 format, `scales` [N] (dequantize_fp8_e4m3);
+ *             MBNB_W_DENSE: W = an already dequantised [N, K] weight of `w_dtype` (Linear8bit's cache, mbnb_gemm_dense's weight).
+ *             K_weight >= K is the row length of W in elements (4-bit: the padded row; otherwise K); pad columns are dropped.
+ * Dispatch.  f16 / bf16 weights with N % 64 == 0, N >= 128, dY 16-byte aligned and a workspace of
+ * mbnb_linear_grad_input_workspace_bytes(...) bytes (256-byte aligned), at EVERY M (there is no fused small-M kernel: the dense
+ * GEMM reads rows past M as zeros, so M = 1 is as correct as M = 4096): a transposed dequantise pass writes Wt [K, N] in `w_dtype`
+ * into the workspace (each element the bits of dequantize_*(W).t()), then the dense GEMM of mbnb_gemm_dense runs with A = dY,
+ * weight = Wt, ldw = N and the library's own plan (slices = 0) -- the same bits as mbnb_gemm_dense(dY, Wt, ..., M, K, N, N, ..., 0)
+ * on a workspace of mbnb_gemm_dense_workspace_bytes(M, K, N) bytes.  The pass needs blocksize >= 32 for the 4-bit formats,
+ * K % 8 == 0 for the others, and an 8-byte (16-byte for MBNB_W_DENSE) aligned W.  Everything else -- f32 weights, other N,
+ * misalignment, NULL / short workspace -- runs a generic kernel that decodes W on the fly (f32 accumulation, same contract).
+ * The query is pure host code: the Wt bytes (K x N x 2 rounded up to 256) plus the GEMM's split-K share where the dense path
+ * applies, 0 where only the generic kernel does.
+ * flags: MBNB_GRAD_TRANSPOSE_ONLY runs the transposed pass alone and writes Wt [K, N] of `w_dtype` into dX (dY and M are
+ * ignored, out_dtype must equal w_dtype; f16 / bf16 only; 4-bit blocksize >= 8, K % 8 == 0 for the other formats, an aligned W,
+ * else MBNB_ERR_UNSUPPORTED): the first step on its own, for tests.
+ * mbnb_last_kernel(): "grad_t+dense" / "grad_t+dense_splitk" / "grad_t" / "grad_generic".
+ * ------------------------------------------------------------------------- */
+enum { MBNB_W_INT8_ROWWISE = 2, MBNB_W_FP8_E4M3 = 3, MBNB_W_DENSE = 4 };
+#define MBNB_GRAD_TRANSPOSE_ONLY 2
+int64_t mbnb_linear_grad_input_workspace_bytes(int64_t M, int64_t N, int64_t K, int w_format, int w_dtype);
+int mbnb_linear_grad_input(const void *dY, int64_t M, int64_t N, int w_format, const void *W, const mbnb_absmax *absmax,
+                           const float *scales, int64_t K, int64_t K_weight, int blocksize, int w_dtype, int out_dtype,
+                           void *dX, void *workspace, int64_t workspace_bytes, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

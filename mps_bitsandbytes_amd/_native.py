@@ -21,6 +21,8 @@ LIB_PATH = os.path.join(_HERE, "libmbnb_hip.so")
 ABI_VERSION = 2   # include/mbnb_hip.h MBNB_ABI_VERSION
 F16, BF16, F32 = 0, 1, 2
 NF4, FP4 = 0, 1
+W_INT8_ROWWISE, W_FP8_E4M3, W_DENSE = 2, 3, 4   # the other weight formats of mbnb_linear_grad_input
+GRAD_TRANSPOSE_ONLY = 2                         # its flags word: the transposed dequantise pass alone
 DTYPE_CODE = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 QUANT_CODE = {"nf4": NF4, "fp4": FP4}
 
@@ -75,6 +77,9 @@ _SIGNATURES = {
     "mbnb_outlier_linear_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "mbnb_outlier_linear": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mbnb_linear_grad_input_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "mbnb_linear_grad_input": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, POINTER(AbsmaxDesc), c_void_p, c_int64, c_int64,
+                                       c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -86,9 +86,13 @@ int embedding_4bit_dispatch(const int64_t *, int64_t, const uint8_t *, const flo
 int embedding_8bit_dispatch(const int64_t *, int64_t, const int8_t *, const float *, int64_t, int64_t, int, int64_t, int, void *, hipStream_t);
 int outlier_linear_dispatch(const void *, int, int64_t, int64_t, const int8_t *, const float *, int64_t, const int64_t *, int64_t, const void *, const void *, void *, void *, int64_t, hipStream_t);
 int64_t outlier_linear_workspace_bytes(int64_t, int64_t, int64_t);
+int64_t grad_input_workspace_bytes(int64_t, int64_t, int64_t, int, int);
+int linear_grad_input_dispatch(const void *, int64_t, int64_t, int, const void *, const AbsmaxView &, const float *, int64_t, int64_t, int, int, int,
+                               void *, void *, int64_t, bool, hipStream_t);
 
 static bool dtype_ok(int d) { return d == MBNB_F16 || d == MBNB_BF16 || d == MBNB_F32; }
 static bool qt_ok(int q) { return q == MBNB_NF4 || q == MBNB_FP4; }
+static bool wfmt_ok(int f) { return qt_ok(f) || f == MBNB_W_INT8_ROWWISE || f == MBNB_W_FP8_E4M3 || f == MBNB_W_DENSE; }
 static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 static int fail(int code, const char *fmt, ...) {
@@ -415,6 +419,43 @@ int mbnb_linear_fp8(const void *X, int dtype, int64_t M, int64_t K, const uint8_
     if (!X || !W || !W_scales || !out) return fail(MBNB_ERR_ARG, "linear_fp8: NULL pointer");
     return linear_fp8_dispatch(X, dtype, M, K, W, W_scales, N, bias, out, workspace, workspace ? workspace_bytes : 0,
                                (flags & MBNB_MATMUL_FUSED_ONLY) != 0, static_cast<hipStream_t>(stream));
+}
+
+int64_t mbnb_linear_grad_input_workspace_bytes(int64_t M, int64_t N, int64_t K, int w_format, int w_dtype) {
+    if (M <= 0 || N <= 0 || K <= 0 || !wfmt_ok(w_format) || !dtype_ok(w_dtype)) return 0;
+    return grad_input_workspace_bytes(M, N, K, w_format, w_dtype);
+}
+
+int mbnb_linear_grad_input(const void *dY, int64_t M, int64_t N, int w_format, const void *W, const mbnb_absmax *absmax, const float *scales,
+                           int64_t K, int64_t K_weight, int blocksize, int w_dtype, int out_dtype, void *dX, void *workspace,
+                           int64_t workspace_bytes, int flags, void *stream) {
+    if (flags & ~MBNB_GRAD_TRANSPOSE_ONLY) return fail(MBNB_ERR_ARG, "linear_grad_input: unknown flags 0x%x", flags);
+    const bool transpose_only = (flags & MBNB_GRAD_TRANSPOSE_ONLY) != 0;
+    if (!wfmt_ok(w_format)) return fail(MBNB_ERR_ARG, "linear_grad_input: bad w_format %d", w_format);
+    if (!dtype_ok(w_dtype) || !dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "linear_grad_input: bad dtype");
+    if (transpose_only && out_dtype != w_dtype) return fail(MBNB_ERR_ARG, "linear_grad_input: the transposed pass writes w_dtype (out_dtype must equal it)");
+    if (M < 0 || N < 0 || K < 0 || workspace_bytes < 0) return fail(MBNB_ERR_ARG, "linear_grad_input: negative size");
+    const bool four = qt_ok(w_format);
+    if (four) {
+        if (!pow2(blocksize) || blocksize > 65536) return fail(MBNB_ERR_ARG, "linear_grad_input: bad blocksize %d", blocksize);
+        if (K_weight < K || K_weight % blocksize || K_weight % 2)
+            return fail(MBNB_ERR_SHAPE, "linear_grad_input: K_weight=%lld inconsistent with K=%lld blocksize=%d", (long long)K_weight, (long long)K,
+                        blocksize);
+    } else if (K_weight != K) {
+        return fail(MBNB_ERR_SHAPE, "linear_grad_input: K_weight=%lld must equal K=%lld for this format", (long long)K_weight, (long long)K);
+    }
+    if (K == 0 || (!transpose_only && M == 0)) return MBNB_OK;
+    if (transpose_only && N == 0) return MBNB_OK;
+    AbsmaxView v{nullptr, nullptr, nullptr, 1};
+    if (four && N > 0)
+        if (int rc = absmax_view(absmax, "linear_grad_input", v)) return rc;
+    if (!four && w_format != MBNB_W_DENSE && N > 0 && !scales) return fail(MBNB_ERR_ARG, "linear_grad_input: NULL scales");
+    if (!dX || (N > 0 && !W) || (!transpose_only && N > 0 && !dY)) return fail(MBNB_ERR_ARG, "linear_grad_input: NULL pointer");
+    if (w_format == MBNB_W_DENSE && w_dtype == MBNB_F32 && transpose_only) return fail(MBNB_ERR_UNSUPPORTED, "linear_grad_input: f32 transpose");
+    const int64_t esz = w_dtype == MBNB_F32 ? 4 : 2;
+    const int64_t ldq = four ? K_weight / 2 : (w_format == MBNB_W_DENSE ? K_weight * esz : K_weight);
+    return linear_grad_input_dispatch(dY, M, N, w_format, W, v, scales, K, ldq, blocksize, w_dtype, out_dtype, dX, workspace,
+                                      workspace ? workspace_bytes : 0, transpose_only, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -534,6 +534,8 @@ def matmul_4bit(
     accumulation, and the result is cast to ``compute_dtype`` (default ``A.dtype``) -- the numerics of the reference's CPU
     branch (functional.py:756-773).
     """
+    if (A.requires_grad or (bias is not None and bias.requires_grad)) and torch.is_grad_enabled():
+        return _MatMul4bitGrad.apply(A, B, quant_state, bias, compute_dtype)   # its forward is this function with grad mode off
     if compute_dtype is None:
         compute_dtype = A.dtype
     _check_device(A, "matmul_4bit")
@@ -672,6 +674,8 @@ def linear_int8(input: Tensor, weight_int8: Tensor, weight_scales: Tensor, bias:
     kernel — the forward of Linear8bit (reference: nn/linear8bit.py:70-102; native binding
     `_C.linear_int8`, mm:1836-1886).
     """
+    if (input.requires_grad or (bias is not None and bias.requires_grad)) and torch.is_grad_enabled():
+        return _LinearInt8Grad.apply(input, weight_int8, weight_scales, bias, dtype)
     _check_device(input, "linear_int8")
     _check_device(weight_int8, "linear_int8")
     if dtype is None:
@@ -702,6 +706,8 @@ def linear_dense(input: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -
     cache (reference nn/linear8bit.py:70-102: `F.linear(x, self._get_weight(), bias)`).  Same slice plan, hence the same bits,
     as ``linear_int8`` / ``matmul_4bit`` on the quantised weight at that shape.  K % 64 == 0, K >= 128.
     """
+    if (input.requires_grad or (bias is not None and bias.requires_grad)) and torch.is_grad_enabled():
+        return _LinearDenseGrad.apply(input, weight, bias)
     _check_device(input, "linear_dense")
     _check_device(weight, "linear_dense")
     dtype = weight.dtype
@@ -767,6 +773,8 @@ def matmul_fp8_e4m3(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: 
     ``input[..., K] @ dequantize_fp8_e4m3(weight[N, K], weight_scales, dtype)^T + bias`` (functional.py:796-807) in one
     kernel: the W8A16 GEMMs of linear_int8 with the FP8 byte decoder in the weight producer.
     """
+    if (input.requires_grad or (bias is not None and bias.requires_grad)) and torch.is_grad_enabled():
+        return _MatMulFP8Grad.apply(input, weight, weight_scales, bias, dtype)
     _check_device(input, "matmul_fp8_e4m3")
     _check_device(weight, "matmul_fp8_e4m3")
     dcode = dtype_code(dtype, "matmul_fp8_e4m3")
@@ -790,6 +798,172 @@ def matmul_fp8_e4m3(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: 
                                             flags, stream_ptr(x2.device)), "matmul_fp8_e4m3")
     out = out.reshape(*lead, N)
     return out.squeeze(0) if is_1d else out
+
+
+# ============================================================================= input gradients (QLoRA training)
+# The reference's CPU path ends every quantised linear in F.linear on the dequantised weight (functional.py:767, :806,
+# nn/linear8bit.py:102), so autograd gives it dX and bias.grad.  Here each forward above takes the autograd route only when grad mode
+# is on and the input or the bias requires grad (otherwise nothing changes, not even a dispatch); the Function's forward is the plain
+# forward (grad mode is off inside it) and its backward runs mbnb_linear_grad_input:
+#   dX = cast(round_w(grad_out.to(w_dtype) @ dequant(W)), A.dtype),   bias.grad = grad_out.to(w_dtype) summed over rows in f32 -> w_dtype -> bias.dtype
+# -- the gradients torch's autograd gives the reference's `F.linear(A.to(w_dtype), dequant(W), bias.to(w_dtype)).to(compute_dtype)`.
+# Only references to the quantised weight and its state are kept for backward: never A, never a dequantised copy of the weight (the
+# weight's transposed dequantised form lives in the backward call's transient workspace).  The weights are buffers: no weight gradient.
+_FMT_INT8, _FMT_FP8, _FMT_DENSE = _native.W_INT8_ROWWISE, _native.W_FP8_E4M3, _native.W_DENSE
+
+
+def _grad_input(dY: Tensor, fmt: int, W: Tensor, desc: Optional[AbsmaxDesc], scales: Optional[Tensor], K: int, K_weight: int,
+                blocksize: int, w_dtype: torch.dtype, out_dtype: torch.dtype) -> Tensor:
+    """dX [M, K] = dY [M, N] (contiguous, w_dtype) . dequant(W) [N, K], through mbnb_linear_grad_input."""
+    M, N = dY.shape
+    w_code = dtype_code(w_dtype, "linear_grad_input")
+    if out_dtype not in _native.DTYPE_CODE:
+        return _grad_input(dY, fmt, W, desc, scales, K, K_weight, blocksize, w_dtype, w_dtype).to(out_dtype)
+    dX = torch.empty(M, K, dtype=out_dtype, device=dY.device)
+    ws_bytes = int(_native.lib().mbnb_linear_grad_input_workspace_bytes(M, N, K, fmt, w_code))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dY.device) if ws_bytes > 0 else None
+    with on_device(dY.device):
+        check(_native.lib().mbnb_linear_grad_input(
+            ptr(dY), M, N, fmt, ptr(W), None if desc is None else ctypes.byref(desc), ptr(scales), K, K_weight, int(blocksize), w_code,
+            _native.DTYPE_CODE[out_dtype], ptr(dX), ptr(ws), ws_bytes, 0, stream_ptr(dY.device)), "linear_grad_input")
+    return dX
+
+
+def _backward(ctx, grad_out: Tensor, bias_index: int, fmt: int, W: Tensor, desc, scales) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(dA, dbias) of one quantised linear; `ctx` carries the shapes and dtypes its forward recorded."""
+    g = grad_out if grad_out.dim() == 2 else grad_out.reshape(-1, grad_out.shape[-1])
+    g = _as(g, ctx.w_dtype)      # an expanded (stride-0) or non-contiguous grad_out becomes a dense w_dtype matrix
+    dA = dbias = None
+    if ctx.needs_input_grad[0]:
+        dA = _grad_input(g, fmt, W, desc, scales, ctx.K, ctx.K_weight, ctx.blocksize, ctx.w_dtype, ctx.a_dtype).reshape(ctx.a_shape)
+    if ctx.needs_input_grad[bias_index]:
+        dbias = g.sum(0, dtype=torch.float32).to(ctx.w_dtype).to(ctx.bias_dtype)
+    return dA, dbias
+
+
+def _record(ctx, A: Tensor, bias: Optional[Tensor], w_dtype: torch.dtype, K: int, K_weight: int, blocksize: int = 0) -> None:
+    ctx.a_shape, ctx.a_dtype = A.shape, A.dtype
+    ctx.bias_dtype = None if bias is None else bias.dtype
+    ctx.w_dtype, ctx.K, ctx.K_weight, ctx.blocksize = w_dtype, K, K_weight, blocksize
+
+
+class _MatMul4bitGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B, quant_state, bias, compute_dtype):
+        out = matmul_4bit(A, B, quant_state, bias, compute_dtype)
+        K = int(quant_state.shape[1])
+        _record(ctx, A, bias, quant_state.dtype, K, _padded(K, quant_state.blocksize), quant_state.blocksize)
+        ctx.save_for_backward(B)
+        ctx.quant_state = quant_state
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (B,) = ctx.saved_tensors
+        st = ctx.quant_state
+        packed = B if B.is_contiguous() else B.contiguous()
+        if packed.dtype != torch.uint8:
+            packed = packed.to(torch.uint8)
+        keep: list = []
+        desc = _absmax_desc(st.absmax if st.absmax.device == packed.device else st.absmax.to(packed.device), st.state2, keep)
+        fmt = _native.QUANT_CODE[st.quant_type]
+        dA, dbias = _backward(ctx, grad_out, 3, fmt, packed, desc, None)   # `keep` holds the absmax tensors until the launch
+        return dA, None, None, dbias, None
+
+
+class _LinearInt8Grad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, weight_int8, weight_scales, bias, dtype):
+        out = linear_int8(input, weight_int8, weight_scales, bias, dtype)
+        K = int(weight_int8.shape[1])
+        _record(ctx, input, bias, out.dtype, K, K)
+        ctx.save_for_backward(weight_int8, weight_scales)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        w, s = ctx.saved_tensors
+        w = w if w.is_contiguous() else w.contiguous()
+        s = _as(s, torch.float32, w.device)
+        dA, dbias = _backward(ctx, grad_out, 3, _FMT_INT8, w, None, s)
+        return dA, None, None, dbias, None
+
+
+class _LinearDenseGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, weight, bias):
+        out = linear_dense(input, weight, bias)
+        K = int(weight.shape[1])
+        _record(ctx, input, bias, weight.dtype, K, K)
+        ctx.save_for_backward(weight)       # Linear8bit's cached dequantised weight: a reference, no copy
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (w,) = ctx.saved_tensors
+        w = w if w.is_contiguous() else w.contiguous()
+        dA, dbias = _backward(ctx, grad_out, 2, _FMT_DENSE, w, None, None)
+        return dA, None, dbias
+
+
+class _MatMulFP8Grad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, weight, weight_scales, bias, dtype):
+        out = matmul_fp8_e4m3(input, weight, weight_scales, bias, dtype)
+        K = int(weight.shape[1])
+        _record(ctx, input, bias, dtype, K, K)
+        ctx.save_for_backward(weight, weight_scales)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        w, s = ctx.saved_tensors
+        w = w if w.is_contiguous() else w.contiguous()
+        s = _as(s, torch.float32, w.device)
+        dA, dbias = _backward(ctx, grad_out, 3, _FMT_FP8, w, None, s)
+        return dA, None, None, dbias, None
+
+
+def _dequantize_t(weight: Tensor, quant_state: Optional[QuantState] = None, scales: Optional[Tensor] = None, fmt: str = "4bit",
+                  dtype: Optional[torch.dtype] = None) -> Tensor:
+    """The transposed dequantise pass of the input gradient on its own: ``dequantize_*(weight).t()`` as a contiguous [K, N] tensor, the
+    bits the backward's GEMM reads.  fmt "4bit" (packed weight + quant_state), "int8" / "fp8" (weight [N, K] + scales, `dtype`) or
+    "dense" (a 16-bit [N, K] weight).  16-bit outputs only.  For tests and tools."""
+    _check_device(weight, "_dequantize_t")
+    keep: list = []
+    desc, s = None, None
+    if fmt == "4bit":
+        N, K = int(quant_state.shape[0]), int(quant_state.shape[1])
+        blocksize, dtype = quant_state.blocksize, quant_state.dtype
+        K_weight = _padded(K, blocksize)
+        _check_absmax_count(quant_state.absmax, N, K_weight, blocksize, "_dequantize_t")
+        W = _as(weight, torch.uint8)
+        if W.numel() * 2 < N * K_weight:
+            raise ValueError(f"packed weight has {W.numel()} bytes, expected {N * K_weight // 2}")
+        desc = _absmax_desc(quant_state.absmax.to(W.device), quant_state.state2, keep)
+        code = _native.QUANT_CODE[quant_state.quant_type]
+    else:
+        W = weight.contiguous()
+        N, K = W.shape
+        K_weight, blocksize = K, 0
+        if fmt == "dense":
+            dtype, code = W.dtype, _FMT_DENSE
+        else:
+            code = {"int8": _FMT_INT8, "fp8": _FMT_FP8}[fmt]
+            s = _as(scales, torch.float32, W.device)
+            if s.numel() != N:
+                raise ValueError(f"scales has {s.numel()} elements, expected {N}")
+    w_code = dtype_code(dtype, "_dequantize_t")
+    out = torch.empty(K, N, dtype=dtype, device=W.device)
+    with on_device(W.device):
+        check(_native.lib().mbnb_linear_grad_input(
+            None, 0, N, code, ptr(W), None if desc is None else ctypes.byref(desc), ptr(s), K, K_weight, int(blocksize), w_code, w_code,
+            ptr(out), None, 0, _native.GRAD_TRANSPOSE_ONLY, stream_ptr(W.device)), "_dequantize_t")
+    return out
 
 
 # ============================================================================= quantized embedding lookups
