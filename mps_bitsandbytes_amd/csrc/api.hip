@@ -8,6 +8,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "dispatch.h"
 
 namespace mbnb {
 
@@ -53,42 +54,6 @@ int check_launch(const char *what) {
     }
     return MBNB_OK;
 }
-
-// launchers (quant_kernels.hip, matmul4_kernels.hip, int8_kernels.hip)
-int quantize_4bit_dispatch(const void *, int, int64_t, int64_t, int64_t, int, int, const float *, uint8_t *, float *, hipStream_t);
-int quantize_4bit_dq_dispatch(const void *, int, int64_t, int64_t, int64_t, int, int, uint8_t *, int8_t *, float *, hipStream_t);
-int dequantize_4bit_dispatch(const uint8_t *, const AbsmaxView &, int64_t, int64_t, int64_t, int, int, int, void *, hipStream_t, int store_policy = 0);
-int quantize_blockwise_dispatch(const void *, int, int64_t, int, const float *, int8_t *, float *, hipStream_t);
-int dequantize_blockwise_dispatch(const int8_t *, int64_t, const float *, int, int, void *, hipStream_t);
-int dequant_absmax_dispatch(const void *, int, int64_t, int64_t, const float *, int64_t, int, float *, hipStream_t);
-int quantize_rowwise_dispatch(const void *, int, int64_t, int64_t, int8_t *, float *, hipStream_t);
-int dequantize_rowwise_dispatch(const int8_t *, const float *, int64_t, int64_t, int, void *, hipStream_t, int store_policy = 0);
-int double_quant_dispatch(const void *, int, int64_t, int64_t, int8_t *, int8_t *, float *, float *, int, int, hipStream_t);
-int matmul_4bit_dispatch(const void *, int64_t, int64_t, const uint8_t *, const AbsmaxView &, int64_t, int64_t, int, int, int, const void *, int, void *, void *, int64_t, int,
-                         hipStream_t);
-int quantize_fp8_dispatch(const void *, int, int64_t, int64_t, uint8_t *, float *, hipStream_t);
-int dequantize_fp8_dispatch(const uint8_t *, const float *, int64_t, int64_t, int, void *, hipStream_t, int store_policy = 0);
-int linear_fp8_dispatch(const void *, int, int64_t, int64_t, const uint8_t *, const float *, int64_t, const void *, void *, void *, int64_t, bool, hipStream_t);
-int64_t matmul4_splitk_slices(int64_t, int64_t, int64_t);
-int64_t gemm_mid_workspace_bytes(int64_t, int64_t, int64_t);
-int64_t gemm_small_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
-int64_t gemm_small8_workspace_bytes(int64_t, int64_t, int64_t);
-int64_t gemm_f32_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
-int64_t gemm_dense_workspace_bytes(int64_t, int64_t, int64_t, int64_t);
-bool gemm_dense_shape(int64_t, int64_t, int64_t, int64_t);
-int64_t gemm_dense_slices(int64_t, int64_t, int64_t);
-int gemm_dense_direct(const void *, const void *, int, const void *, int, void *, int64_t, int64_t, int64_t, int64_t, float *, int64_t, int, int,
-                      hipStream_t);
-int matmul_int8_dispatch(const int8_t *, const int8_t *, const float *, const float *, int64_t, int64_t, int64_t, int, void *, void *, hipStream_t);
-int64_t matmul_int8_workspace_bytes(int64_t, int64_t, int64_t);
-int linear_int8_dispatch(const void *, int, int64_t, int64_t, const int8_t *, const float *, int64_t, const void *, void *, void *, int64_t, bool, hipStream_t);
-int embedding_4bit_dispatch(const int64_t *, int64_t, const uint8_t *, const float *, int64_t, int64_t, int, int, int, int64_t, int, void *, hipStream_t);
-int embedding_8bit_dispatch(const int64_t *, int64_t, const int8_t *, const float *, int64_t, int64_t, int, int64_t, int, void *, hipStream_t);
-int outlier_linear_dispatch(const void *, int, int64_t, int64_t, const int8_t *, const float *, int64_t, const int64_t *, int64_t, const void *, const void *, void *, void *, int64_t, hipStream_t);
-int64_t outlier_linear_workspace_bytes(int64_t, int64_t, int64_t);
-int64_t grad_input_workspace_bytes(int64_t, int64_t, int64_t, int, int);
-int linear_grad_input_dispatch(const void *, int64_t, int64_t, int, const void *, const AbsmaxView &, const float *, int64_t, int64_t, int, int, int,
-                               void *, void *, int64_t, bool, hipStream_t);
 
 static bool dtype_ok(int d) { return d == MBNB_F16 || d == MBNB_BF16 || d == MBNB_F32; }
 static bool qt_ok(int q) { return q == MBNB_NF4 || q == MBNB_FP4; }

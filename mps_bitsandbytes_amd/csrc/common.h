@@ -235,43 +235,16 @@ __device__ __forceinline__ float wave_sum(float v) {
 // and cannot collide with a hipError_t (> 0; hipErrorInvalidValue == 1) or an MBNB_ERR_* code (-1 .. -3).
 constexpr int MBNB_NOT_APPLICABLE = -1000;
 
-// LDS-DMA issue in the pipelined GEMMs (gemm_dense.h, gemm_dense128.h, gemm_i8_inplace.h, gemm_small.h, gemm_small8.h).  1 (default): four
-// pieces share ONE M0 write -- the instruction's 12-bit offset is added to the LDS address and to the global address alike, so piece
-// 4 g + m goes out with offset 1024 m from a per-lane offset that is 1024 m smaller (tools/exp/ab_m0.py: same bits; k_gemm_dense 93.4 ->
-// 92.7 us at 4096^3).  0 (diagnostic builds): one s_mov m0 + s_nop per piece.
-#ifndef GD_M0_GROUP
-#define GD_M0_GROUP 1
-#endif
-// k_gemm_dense's 16-bit epilogue stages the wave's tile through its private LDS in parts of 16 * GD_EPI_GROUPS rows: with one 16-row group
-// per part the first stores leave after 1/8 of the conversions instead of 1/2 (tools/exp/ab_dense_epilogue.py: same bits; 91.9 -> 91.1 us at
-// 4096^3, 29.8 -> 28.6 us at 4000 x 4096 x 1024).  4 (diagnostic builds): two halves of 64 rows.
-#ifndef GD_EPI_GROUPS
-#define GD_EPI_GROUPS 1
-#endif
-// Cache policy of the 16-bit epilogue stores of k_gemm_dense and k_gemm_dense128 (store_out16).  1 (default): write-through "sc1" -- the tile's
-// bytes are not read again by this launch and leave nothing for the end of the launch to drain (tools/exp/ab_dense_store.py: k_gemm_dense alone
-// 93.9 -> 93.8 us, inside the step 104.5 -> 103.8 us at 4096^3, 284.0 -> 283.1 at 11008 x 4096; ab_epilogue_store.py: the 1024-row step on
-// k_gemm_dense128 43.0 -> 42.1 us).  Diagnostic builds: 0 nontemporal (round 2: 98.5 -> 95.6 us against plain stores), 2 "sc1 nt",
-// 3 "sc0 sc1 nt", 4 plain.  k_gemm_i8_inplace keeps nontemporal stores (store_out16_nt; "sc1" there: 53.0 -> 53.6 us), and so do the
-// kernels that are off by default (not measured).
-#ifndef GD_EPI_STORE
-#define GD_EPI_STORE 1
-#endif
 // One aligned 16-byte f32 store, write-through ("sc1"): split-K partials, read next by the reduction launch on other XCDs.
 __device__ __forceinline__ void store_f32x4_wt(float *dst, f32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory"); }
 __device__ __forceinline__ void store_out16_nt(u32x4 *dst, u32x4 v) { __builtin_nontemporal_store(v, dst); }
+// Cache policy of the 16-bit epilogue stores of k_gemm_dense and k_gemm_dense128: write-through "sc1" -- the tile's bytes are not read
+// again by this launch and leave nothing for the end of the launch to drain (k_gemm_dense alone 93.9 -> 93.8 us against nontemporal, inside
+// the step 104.5 -> 103.8 us at 4096^3, 284.0 -> 283.1 at 11008 x 4096; the 1024-row step on k_gemm_dense128 43.0 -> 42.1 us;
+// profiles/r03_epilogue_store_policy_ab.txt).  k_gemm_i8_inplace keeps nontemporal stores (store_out16_nt; "sc1" there: 53.0 -> 53.6 us),
+// and so do the kernels that are off by default (not measured).
 __device__ __forceinline__ void store_out16(u32x4 *dst, u32x4 v) {
-#if GD_EPI_STORE == 0
-    __builtin_nontemporal_store(v, dst);
-#elif GD_EPI_STORE == 1
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-#elif GD_EPI_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(dst), "v"(v) : "memory");
-#elif GD_EPI_STORE == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(dst), "v"(v) : "memory");
-#else
-    *dst = v;
-#endif
 }
 void set_error(const char *fmt, ...);
 void set_kernel_name(const char *name);

@@ -45,19 +45,6 @@ template <int N, class F> __device__ __forceinline__ void gd_static_for(F &&f) {
     gd_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F &&>(f));
 }
 
-#ifndef GD_ABL
-#define GD_ABL 0        // diagnostic builds (timing only): 1 no LDS-DMA pieces in the k-loop, 2 no fragment reads in the k-loop, 4 no barriers in the k-loop
-#endif
-#ifndef GD_B_TILE_MAJOR
-#define GD_B_TILE_MAJOR 0   // diagnostic builds (tools/exp/dense_tm_exp.hip): Wd is a TILE-MAJOR scratch [n tile of 256 rows][k tile of 64][row][128 B] --
-                            // every LDS-DMA piece of the weight operand is 1 KiB contiguous instead of 8 lines `ldw` apart (uniform 256-wide tiles only)
-#endif
-#ifndef GD_STAMPS
-#define GD_STAMPS 0     // diagnostic builds: 1 the vmcnt wait of barrier 2, 2 barrier 2 itself, 3 the lgkmcnt wait of barrier 1, 4 barrier 1 itself
-#endif
-#if GD_STAMPS
-__device__ unsigned long long g_gd_stamps[16];
-#endif
 constexpr int GD_LDS = 4 * P_IMG;   // A0 A1 B0 B1; the epilogue's store staging (4 x 16.5 KiB) fits inside
 
 // Slot plan of a k-step for a wave tile of 8 (n) x FM (m) fragments of 16 x 16: NS = 16 FM slots, NR = 8 + FM fragment reads
@@ -146,47 +133,34 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
     // 8p + (l >> 3), source chunk (l & 7) ^ ((row >> 1) & 7).  The ROW goes into the per-lane offset (8 + 8 VGPRs that never
     // change), the k position into the scalar offset: the descriptor's range check covers the per-lane offset only
     // (the scalar offset is excluded from it), and num_records = rows x pitch makes every row past M / N read as zeros
-    // without touching memory -- no clamps, no reads outside the operands.
+    // without touching memory -- no clamps, no reads outside the operands.  (A tile-major weight scratch, every B piece 1 KiB
+    // contiguous instead of 8 lines `ldw` apart, measured the same: 90.23 vs 90.33 us at 4096^3, profiles/r04_dense_tile_major_ab.txt.)
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
     i32x4_t rs_a, rs_b;
     {
-#if GD_B_TILE_MAJOR
-        // tile-major scratch: the tile column's blocks [K / 64][256 rows][64 k] follow each other; rows past N are zero in the scratch
-        const uint64_t pa = reinterpret_cast<uint64_t>(X + m0 * K + k_begin), pb = reinterpret_cast<uint64_t>(Wd + (n0 >> 8) * (K >> 6) * 16384 + (k_begin >> 6) * 16384);
-        const int64_t rows_a = M - m0 < TM ? M - m0 : TM, rows_b = 256;
-        rs_a = i32x4_t{(int)(uint32_t)pa, (int)(uint32_t)(pa >> 32), (int)(rows_a * K * 2), 0x00020000};
-        rs_b = i32x4_t{(int)(uint32_t)pb, (int)(uint32_t)(pb >> 32), (int)((k_len >> 6) * 32768), 0x00020000};
-        (void)rows_b;
-#else
         const uint64_t pa = reinterpret_cast<uint64_t>(X + m0 * K + k_begin), pb = reinterpret_cast<uint64_t>(Wd + n0 * ldw + k_begin);
         const int64_t rows_a = M - m0 < TM ? M - m0 : TM, rows_b = N - n0 < TN ? N - n0 : TN;
         rs_a = i32x4_t{(int)(uint32_t)pa, (int)(uint32_t)(pa >> 32), (int)(rows_a * K * 2), 0x00020000};
         rs_b = i32x4_t{(int)(uint32_t)pb, (int)(uint32_t)(pb >> 32), (int)(rows_b * ldw * 2), 0x00020000};
-#endif
     }
     int voff_a[FM], voff_b[FN];
 #pragma unroll
     for (int pl = 0; pl < FN; pl++) {
         const int row = 8 * (FN * wave + pl) + (lane >> 3);
-#if GD_B_TILE_MAJOR
-        voff_b[pl] = row * 128 + 16 * ((lane & 7) ^ ((row >> 1) & 7));
-#else
         voff_b[pl] = (int)(row * ldw * 2) + 16 * ((lane & 7) ^ ((row >> 1) & 7));
-#endif
     }
 #pragma unroll
     for (int pl = 0; pl < FM; pl++) {
         const int row = 8 * (FM * wave + pl) + (lane >> 3);
         voff_a[pl] = (int)(row * K * 2) + 16 * ((lane & 7) ^ ((row >> 1) & 7));
     }
-#if GD_M0_GROUP
     // Pieces 4 g .. 4 g + 3 of an operand share ONE M0 value: the instruction's 12-bit offset is added to the LDS address and to the
-    // global address alike, so piece 4 g + m is issued with offset 1024 m from a per-lane offset that is 1024 m smaller.
+    // global address alike, so piece 4 g + m is issued with offset 1024 m from a per-lane offset that is 1024 m smaller (same bits as
+    // an s_mov m0 + s_nop per piece; 93.4 -> 92.7 us at 4096^3, profiles/r03_m0_group_ab.txt).  The other pipelined GEMMs do the same.
 #pragma unroll
     for (int pl = 0; pl < FN; pl++) voff_b[pl] -= (pl & 3) * 1024;
 #pragma unroll
     for (int pl = 0; pl < FM; pl++) voff_a[pl] -= (pl & 3) * 1024;
-#endif
     const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)smem;
     // The wave-uniform operands of the DMA travel in a DmaCtx made INSIDE the loop copy that uses them: defined there by
     // readfirstlane they are SGPRs for certain (across the per-wave branch the compiler otherwise re-derives them in
@@ -209,19 +183,11 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
         const uint32_t dst = (q < FM ? c.lwa : c.lwb) + (uint32_t)(stage * P_IMG + pl * 1024);
         const int vo = (q < FM) ? voff_a[pl] : voff_b[pl];
         const i32x4_t rs = (q < FM) ? c.ra : c.rb;
-#if GD_B_TILE_MAJOR
-        if constexpr (q >= FM) kb = __builtin_amdgcn_readfirstlane(kb << 8);     // k tile t: byte 128 t of a row-major row, block 32768 t of the tile-major scratch
-#endif
-#if GD_M0_GROUP
         if constexpr ((pl & 3) != 0) {
             asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(kb), "n"((pl & 3) * 1024) : "memory", "m0");
         } else {
-            const uint32_t dstg = (q < FM ? c.lwa : c.lwb) + (uint32_t)(stage * P_IMG + pl * 1024);
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dstg), "v"(vo), "s"(rs), "s"(kb) : "memory", "m0");
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(vo), "s"(rs), "s"(kb) : "memory", "m0");
         }
-#else
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(vo), "s"(rs), "s"(kb) : "memory", "m0");
-#endif
     };
 
     // ---- fragment reads (16 x 16 x 32): lane l = row l & 15 of the fragment's 16, k chunk 4 ks + (l >> 4), swizzled by the row
@@ -256,10 +222,6 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
     asm volatile("" ::: "memory");
     gd_static_for<Plan::NR>([&](auto n) { read_one(0, std::integral_constant<int, 0>{}, n); });
 
-#if GD_STAMPS
-    uint64_t gd_sum = 0, gd_cnt = 0, gd_t0 = 0;      // diagnostic builds (tools/exp/dense_stamps.hip): cycles of one wait / barrier, summed over the k-steps
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gd_t0) :: "memory");
-#endif
     // ---- one k-step = Plan::NS fenced slots.  Stage C holds tile j, stage Nn tile j+1 (landing); WO = the wave's slot offset.
     auto kstep = [&](auto cc, auto first, auto wo_, int j, const DmaCtx &dc) {
         constexpr int C = decltype(cc)::value, Nn = C ^ 1, WO = decltype(wo_)::value;
@@ -268,29 +230,13 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
         gd_static_for<Plan::NS>([&](auto tt) {
             constexpr int t = decltype(tt)::value, ks = t / (FN * FM), f = (t % (FN * FM)) / FM, g = t % FM;
             if constexpr (t == Plan::B1) {
-#if GD_STAMPS == 3
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) :: "memory"); gd_sum += b_ - a_; gd_cnt++; }
-#else
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#if GD_STAMPS == 4
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) :: "memory"); gd_sum += b_ - a_; gd_cnt++; }
-#else
-                if constexpr (!(GD_ABL & 4)) __builtin_amdgcn_s_barrier();
-#endif
+                __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
             if constexpr (t == Plan::B2) {
-#if GD_STAMPS == 1
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_waitcnt vmcnt(%2)\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) : "n"(Plan::NP) : "memory"); gd_sum += b_ - a_; gd_cnt++; }
-#else
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Plan::NP) : "memory");
-#endif
-#if GD_STAMPS == 2
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) :: "memory"); gd_sum += b_ - a_; gd_cnt++; }
-#else
-                if constexpr (!(GD_ABL & 4)) __builtin_amdgcn_s_barrier();
-#endif
+                __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
             if constexpr (I8) {
@@ -305,11 +251,11 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
             } else {
                 acc[f][g] = Mfma16<T>::run(wf[ks][f], xf[ks][g], acc[f][g]);
             }
-            if constexpr (!(GD_ABL & 2) && (t % Plan::RS1) == 0 && t / Plan::RS1 < Plan::NR)
+            if constexpr ((t % Plan::RS1) == 0 && t / Plan::RS1 < Plan::NR)
                 read_one(C, std::integral_constant<int, 1>{}, std::integral_constant<int, (t / Plan::RS1) % Plan::NR>{});
-            if constexpr (!(GD_ABL & 2) && t >= Plan::R0 && t < Plan::R0 + Plan::NR)
+            if constexpr (t >= Plan::R0 && t < Plan::R0 + Plan::NR)
                 read_one(Nn, std::integral_constant<int, 0>{}, std::integral_constant<int, (t - Plan::R0) % Plan::NR>{});
-            if constexpr (!(GD_ABL & 1) && t >= Plan::D0 && t < Plan::D0 + Plan::NP * Plan::DS && ((t - Plan::D0) % Plan::DS) == WO)
+            if constexpr (t >= Plan::D0 && t < Plan::D0 + Plan::NP * Plan::DS && ((t - Plan::D0) % Plan::DS) == WO)
                 issue_piece(std::integral_constant<int, ((t - Plan::D0) / Plan::DS) % Plan::NP>{}, C, kb2, dc);
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -334,16 +280,6 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
         else main_loop(std::integral_constant<int, 1>{});
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if GD_STAMPS
-    {
-        uint64_t gd_t1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gd_t1) :: "memory");
-        if (blockIdx.x == 17 && (threadIdx.x & 63) == 0) {
-            unsigned long long *o = g_gd_stamps + 4 * (threadIdx.x >> 6);
-            o[0] = gd_sum; o[1] = gd_cnt; o[2] = gd_t1 - gd_t0;
-        }
-    }
-#endif
 
     // ---- epilogue: acc[f][g][r] = out[m0 + 16 FM wm + 16 g + (lane & 15)][n0 + 16 FN wn + 16 f + 4 (lane >> 4) + r]
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -392,8 +328,10 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
             }
         return;
     }
-    // 16-bit outputs: the wave's tile goes through its private 16.5 KiB of LDS (264-byte row pitch) in two halves of 64 rows
-    // and leaves as 16-byte stores of whole 256-byte row segments
+    // 16-bit outputs: the wave's tile goes through its private 16.5 KiB of LDS (264-byte row pitch) in parts of 16 rows and leaves
+    // as 16-byte stores of whole 256-byte row segments.  One 16-row group per part: the first stores leave after 1/8 of the
+    // conversions instead of 1/2 (same bits; 91.9 -> 91.1 us against halves of 64 rows at 4096^3, 29.8 -> 28.6 us at 4000 x 4096 x 1024,
+    // profiles/r03_dense_epilogue_parts_ab.txt)
     constexpr int ROWB = 264;
     char *wave_lds = smem + wave * 64 * ROWB;
     uint16_t *out = static_cast<uint16_t *>(out_v);
@@ -495,7 +433,7 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
     // loops (as run-time tests they became four branches per fragment; bias loads in the loops cost a memory latency each)
     auto epilogue16 = [&](auto wo_t, auto wb_t) {
     constexpr bool WO = decltype(wo_t)::value, WB = decltype(wb_t)::value;
-    constexpr int GP = (FM % GD_EPI_GROUPS == 0) ? GD_EPI_GROUPS : 4;   // 16-row groups per staged part
+    constexpr int GP = 1;   // 16-row groups per staged part
     gd_static_for<FM / GP>([&](auto hh) {
         constexpr int H = decltype(hh)::value;
         const int64_t m_base = m0 + wm * 16 * FM + 16 * GP * H;
@@ -580,7 +518,7 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
 #pragma unroll
                 for (int p = 0; p < 4 * GP; p++) {
                     const int64_t m = m_base + p * 4 + (lane_e >> 4);
-                    // not read again by this launch, and 256 workgroups store 32 MB at once: write-through (common.h GD_EPI_STORE; round 2's
+                    // not read again by this launch, and 256 workgroups store 32 MB at once: write-through (common.h store_out16; round 2's
                     // nontemporal stores: 98.5 -> 95.6 us at 4096^3 against plain ones, tools/exp/ab_dense.py variants 1008 / 1040)
                     if (m < M) store_out16(reinterpret_cast<u32x4 *>(out + m * N + n), piece[p]);
                 }

@@ -6,13 +6,12 @@
 //   [0, wd_bytes)                    Wd [N, K_weight] in the compute dtype, wd_bytes = N * K_weight * 2 rounded up to 256
 //   [wd_bytes, + slices * M * N * 4) f32 partials of the split-K slices (none when slices == 1)
 #include <cstdio>
+#include "dispatch.h"
 #include "gemm_dense.h"
 #include "gemm_dense128.h"
 #include "gemm_mid.h"
 
 namespace mbnb {
-
-int dequantize_4bit_dispatch(const uint8_t *, const AbsmaxView &, int64_t, int64_t, int64_t, int, int, int, void *, hipStream_t, int store_policy = 0);
 
 // The policy, from tools/exp/sweep_dense.py (profiles/r02_dense_sweep.txt, r02_dense_sweep2.txt, r02_dense_sweep3.txt).  The
 // path is taken from 256 rows and 1.5 M outputs up (gemm_dense_shape; below that the fused split-K kernels win).  A plan = (wave-tile m fragments FM: 8 -> 256 x 256 tiles, 4 -> 256 n x 128 m tiles; K slices s), the
@@ -246,9 +245,6 @@ int matmul_4bit_dense_path(const void *A, int64_t M, int64_t K, const uint8_t *p
     set_kernel_name(slices > 1 ? "dequant+dense_splitk" : "dequant+dense");   // tile shape: gemm_dense_plan (not part of the name)
     return rc;
 }
-
-int dequantize_rowwise_dispatch(const int8_t *, const float *, int64_t, int64_t, int, void *, hipStream_t, int store_policy = 0);
-int dequantize_fp8_dispatch(const uint8_t *, const float *, int64_t, int64_t, int, void *, hipStream_t, int store_policy = 0);
 
 // Linear8bit.forward / LinearFP8.forward at large M (nn/linear8bit.py:70-102, functional.py:796-807): the reference's own two
 // steps -- dequantize_rowwise / dequantize_fp8_e4m3 into the compute dtype, then F.linear -- on the workspace.  Same policy

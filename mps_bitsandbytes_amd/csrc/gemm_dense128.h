@@ -18,19 +18,6 @@
 
 namespace mbnb {
 
-#ifndef G128_EPI_ONE_PART
-#define G128_EPI_ONE_PART 0   // diagnostic builds: 1 = the 16-bit epilogue converts the whole 64-row tile before its first store
-#endif
-#ifndef G128_ABL
-#define G128_ABL 0       // diagnostic builds: 1 no LDS-DMA pieces in the loop, 2 no fragment reads in the loop (timing only)
-#endif
-#ifndef G128_STAMPS
-#define G128_STAMPS 0     // diagnostic builds: 1 the vmcnt wait of the k-step's barrier, 2 the barrier itself
-#endif
-#if G128_STAMPS
-__device__ unsigned long long g_d128_stamps[16];
-#endif
-
 constexpr int G128_STAGE = 32768;            // A image 16 KiB (128 rows x 128 B) + B image 16 KiB
 constexpr int G128_LDS = 3 * G128_STAGE;     // the epilogue's staging (4 x 64 rows x 136 B) fits inside
 
@@ -81,8 +68,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
     for (int pl = 0; pl < 4; pl++) {
         const int row = 8 * (4 * wave + pl) + (lane >> 3);
         const int sw = 16 * ((lane & 7) ^ ((row >> 1) & 7));
-        voff_a[pl] = (int)(row * K * 2) + sw - GD_M0_GROUP * pl * 1024;       // the piece's 1024 pl travel in the instruction offset (issue_piece)
-        voff_b[pl] = (int)(row * ldw * 2) + sw - GD_M0_GROUP * pl * 1024;
+        voff_a[pl] = (int)(row * K * 2) + sw - pl * 1024;       // the piece's 1024 pl travel in the instruction offset (issue_piece)
+        voff_b[pl] = (int)(row * ldw * 2) + sw - pl * 1024;
     }
     const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)smem;
     struct DmaCtx { i32x4_t ra, rb; uint32_t lw; };
@@ -103,8 +90,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
         const int vo = (q < 4) ? voff_a[pl] : voff_b[pl];
         const i32x4_t rs = (q < 4) ? c.ra : c.rb;
         // the operand's four pieces share ONE M0 write: the instruction offset (added to the LDS address and to the global address alike)
-        // carries the piece, the per-lane offsets are 1024 pl smaller (gemm_dense.h, GD_M0_GROUP)
-        if constexpr (GD_M0_GROUP && pl != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(kb), "n"(pl * 1024) : "memory", "m0");
+        // carries the piece, the per-lane offsets are 1024 pl smaller (gemm_dense.h)
+        if constexpr (pl != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(kb), "n"(pl * 1024) : "memory", "m0");
         else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(vo), "s"(rs), "s"(kb) : "memory", "m0");
     };
 
@@ -147,10 +134,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
     asm volatile("" ::: "memory");
     gd_static_for<16>([&](auto n) { read_frag(0, I0{}, n); });
 
-#if G128_STAMPS
-    uint64_t g_sum = 0, g_cnt = 0, g_t0 = 0;      // diagnostic builds (tools/exp/d128_stamps.hip)
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(g_t0) :: "memory");
-#endif
     // ---- one k-step: tile j in registers (parity P), tile j+1 in stage s1 (landing), tile j+2 requested into stage s2
     auto kstep = [&](auto pp, auto first, auto wo_, int s1, int s2, int j, const DmaCtx &dc) {
         constexpr int P = decltype(pp)::value, WO = decltype(wo_)::value;
@@ -162,26 +145,18 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
             if constexpr (t == 18) {
                 // tile j+1 (requested one k-step ago) has landed for this wave; behind the barrier for all of them -- and every wave
                 // has finished reading tile j-1's stage... (its reads were issued in k-step j-1 and waited for by its MFMAs)
-#if G128_STAMPS == 1
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_waitcnt vmcnt(8)\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) :: "memory"); g_sum += b_ - a_; g_cnt++; }
-#else
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the reads of tile j (issued a k-step ago) are complete: free by now
-#if G128_STAMPS == 2
-                { uint64_t a_, b_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "=s"(b_) :: "memory"); g_sum += b_ - a_; g_cnt++; }
-#else
                 __builtin_amdgcn_s_barrier();
-#endif
                 asm volatile("" ::: "memory");
             }
             if constexpr (FIRST && ks == 0) mfma_zero(acc[f][g], wf[P][ks][f], xf[P][ks][g]);
             else mfma_acc(acc[f][g], wf[P][ks][f], xf[P][ks][g]);
             // pieces of tile j+2: stage s2 held tile j-1, which every wave finished reading before the barrier of k-step j-1
-            if constexpr (!(G128_ABL & 1) && t >= WO && t < WO + 16 && ((t - WO) & 1) == 0)
+            if constexpr (t >= WO && t < WO + 16 && ((t - WO) & 1) == 0)
                 issue_piece(std::integral_constant<int, ((t - WO) >> 1) & 7>{}, s2, kb2, dc);
             // fragments of tile j+1 (16 reads) behind the barrier: slots 18 .. 31 (two in the first two slots)
-            if constexpr (!(G128_ABL & 2) && t >= 18) {
+            if constexpr (t >= 18) {
                 constexpr int n0_ = t == 18 ? 0 : (t == 19 ? 2 : t - 16);
                 read_frag(s1, PN_{}, std::integral_constant<int, n0_ & 15>{});
                 if constexpr (t < 20) read_frag(s1, PN_{}, std::integral_constant<int, (n0_ + 1) & 15>{});
@@ -206,16 +181,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
     if ((wave & 1) == 0) main_loop(I0{});
     else main_loop(I1{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if G128_STAMPS
-    {
-        uint64_t g_t1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(g_t1) :: "memory");
-        if (blockIdx.x == 17 && (threadIdx.x & 63) == 0) {
-            unsigned long long *o = g_d128_stamps + 4 * (threadIdx.x >> 6);
-            o[0] = g_sum; o[1] = g_cnt; o[2] = g_t1 - g_t0;
-        }
-    }
-#endif
 
     // ---- epilogue: acc[f][g][r] = out[m0 + 64 wm + 16 g + (lane & 15)][n0 + 64 wn + 16 f + 4 (lane >> 4) + r]
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -264,71 +229,13 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
             bias_all[f] = u32x2{t[0] | (t[1] << 16), t[2] | (t[3] << 16)};
         }
     }
-#if G128_EPI_ONE_PART
-    auto epilogue16 = [&](auto wb_t) {
-        constexpr bool WB = decltype(wb_t)::value;
-#pragma unroll
-        for (int f = 0; f < 4; f++) {
-            const int nl = 16 * f + 4 * efq;
-            float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if constexpr (WB) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) bv[e] = unpack_lo<T>(bias_all[f][e >> 1] >> (16 * (e & 1)));
-            }
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    float sv;
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(sv) : "a"(acc[f][g][e]));
-                    v[e] = sv + bv[e];
-                }
-                if (!same_out) {
-#pragma unroll
-                    for (int e = 0; e < 4; e++) v[e] = to_f32(from_f32<T>(v[e]));
-                }
-                u32x2 pk;
-                if (out_dtype == MBNB_F16) pk = u32x2{pack2<f16_t>(v[0], v[1]), pack2<f16_t>(v[2], v[3])};
-                else pk = u32x2{pack2<bf16_t>(v[0], v[1]), pack2<bf16_t>(v[2], v[3])};
-                *reinterpret_cast<u32x2 *>(wave_lds + (16 * g + er16) * ROWB + nl * 2) = pk;
-            }
-        }
-        const int ch = lane_e & 7;   // 8 rows x 8 chunks of 16 B per instruction
-        u32x4 piece[8];
-#pragma unroll
-        for (int p = 0; p < 8; p++) {
-            const char *srcp = wave_lds + (p * 8 + (lane_e >> 3)) * ROWB + ch * 16;
-            const u32x2 lo = *reinterpret_cast<const u32x2 *>(srcp), hi = *reinterpret_cast<const u32x2 *>(srcp + 8);
-            piece[p] = u32x4{lo[0], lo[1], hi[0], hi[1]};
-        }
-        const int64_t n = n_base + ch * 8;
-        if (n < N) {
-            if (vec_ok && n + 8 <= N) {
-#pragma unroll
-                for (int p = 0; p < 8; p++) {
-                    const int64_t m = m_base + p * 8 + (lane_e >> 3);
-                    if (m < M) store_out16(reinterpret_cast<u32x4 *>(out + m * N + n), piece[p]);
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < 8; p++) {
-                    const int64_t m = m_base + p * 8 + (lane_e >> 3);
-                    if (m >= M) continue;
-#pragma unroll
-                    for (int e = 0; e < 8; e++)
-                        if (n + e < N) out[m * N + n + e] = (uint16_t)(piece[p][e >> 1] >> (16 * (e & 1)));
-                }
-            }
-        }
-    };
-#else
     auto epilogue16 = [&](auto wb_t) {
         constexpr bool WB = decltype(wb_t)::value;
         const int ch = lane_e & 7;   // 8 rows x 8 chunks of 16 B per instruction
         const int64_t n = n_base + ch * 8;
         // four parts of 16 rows, each through its own rows of the staging: the first stores leave after a quarter of the conversions
-        // (the same split as k_gemm_dense's, common.h GD_EPI_GROUPS)
+        // (the same split as k_gemm_dense's; 32.4 -> 32.1 us against one part of 64 rows at 1024 x 4096^2, same bits,
+        // profiles/r03_dense_epilogue_parts_ab.txt)
 #pragma unroll
         for (int g = 0; g < 4; g++) {
 #pragma unroll
@@ -378,7 +285,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_dense128(const T *__restrict__ 
             }
         }
     };
-#endif
     if (bias != nullptr) epilogue16(std::true_type{});
     else epilogue16(std::false_type{});
 }

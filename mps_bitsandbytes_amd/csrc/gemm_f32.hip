@@ -12,11 +12,10 @@
 // takes 64 cycles per 32 x 32 x 2 product, so the loads and the LDS port idle most of the time: the kernel is bound by
 // the f32 matrix rate (157 TFLOP/s nominal).  A lane's four consecutive k of a fragment row are one ds_read_b128; the
 // MFMA's two k positions are the lane halves, so operand j of half h multiplies k = 8 q + 4 h + j on both sides.
+#include "dispatch.h"
 #include "gemm_mid.h"
 
 namespace mbnb {
-
-int dequantize_4bit_dispatch(const uint8_t *, const AbsmaxView &, int64_t, int64_t, int64_t, int, int, int, void *, hipStream_t, int store_policy = 0);
 
 constexpr int GF_BK = 32;
 constexpr int GF_PITCH = 36;   // floats per LDS row (144 bytes)

@@ -79,9 +79,7 @@ struct GfPlan {
     }
 };
 
-// ABL (diagnostic builds under tools/exp only; the product instantiates 0): 1 no table lookups, 2 no products, 4 no image writes,
-// 8 no byte extract / pack either (with 7: no decode work at all), 16 no raw / absmax LDS-DMA, 32 no raw / absmax LDS reads
-template <typename T, bool NESTED, int ABL = 0>
+template <typename T, bool NESTED>
 __global__ __launch_bounds__(256, 1) void k_gemm_fused4(const T *__restrict__ X, typename Q4ProducerRT<T, NESTED>::Params wp,
                                                         const T *__restrict__ bias, void *__restrict__ out_v, int out_dtype,
                                                         int64_t M, int64_t N, int64_t K) {
@@ -267,18 +265,12 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fused4(const T *__restrict__ X,
     // unit u of the tile of parity P: byte u of the lane's 32
     auto dec_lookup = [&](auto pp, auto uu) {
         constexpr int P = decltype(pp)::value, u = decltype(uu)::value;
-        if constexpr (ABL & 8) return;
         uint32_t off;
         const uint32_t w = rw[P][u >> 2];
         if constexpr ((u & 3) == 0) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(w));
         else if constexpr ((u & 3) == 1) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(off) : "v"(w));
         else if constexpr ((u & 3) == 2) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off) : "v"(w));
         else asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(off) : "v"(w));
-        if constexpr (ABL & 1) {
-            Lr[u % 3][0] = __builtin_bit_cast(float, off);
-            Lr[u % 3][1] = __builtin_bit_cast(float, off + 1u);
-            return;
-        }
         const f32x2 v = *reinterpret_cast<const f32x2 *>(lut2 + off);
         Lr[u % 3][0] = v[0];
         Lr[u % 3][1] = v[1];
@@ -288,28 +280,23 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fused4(const T *__restrict__ X,
     auto dec_mul1 = [&](auto pp, auto uu) {
         constexpr int P = decltype(pp)::value, u = decltype(uu)::value;
         const float l = Lr[u % 3][0], a = am[P];
-        float r = l;
-        if constexpr (!(ABL & 2)) asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(l), "v"(a));
+        float r;
+        asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(l), "v"(a));
         P0 = r;
     };
     auto dec_mul2 = [&](auto pp, auto uu) {
         constexpr int P = decltype(pp)::value, u = decltype(uu)::value;
         const float l = Lr[u % 3][1], a = am[P];
-        float r = l;
-        if constexpr (!(ABL & 2)) asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(l), "v"(a));
+        float r;
+        asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(l), "v"(a));
         P1 = r;
     };
     auto dec_pack = [&](auto uu) {
         constexpr int u = decltype(uu)::value;
-        if constexpr (ABL & 8) return;
         ob[(u >> 2) & 1][u & 3] = pack2<T>(P0, P1);
     };
     auto dec_write = [&](int stage, auto cc) {
         constexpr int c = decltype(cc)::value;
-        if constexpr (ABL & 4) {
-            if constexpr (!(ABL & 8)) asm volatile("" ::"v"(ob[c & 1]));     // keeps the producing instructions alive
-            return;
-        }
         *reinterpret_cast<u32x4 *>(smem + (wb_k ^ (c << 4)) + stage * P_IMG) = ob[c & 1];
     };
 
@@ -413,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fused4(const T *__restrict__ X,
             }
             if constexpr (t == GfPlan::B2) {
                 // everything issued one k-step ago has landed: A(j+1), raw(j+2), (absmax); own image writes are done
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ABL & 16) ? GfPlan::NP : GfPlan::NP + 2) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GfPlan::NP + 2) : "memory");
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
@@ -437,20 +424,18 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fused4(const T *__restrict__ X,
             if constexpr (t >= GfPlan::B1 && t < GfPlan::B1 + 4 * 11 && ((t - GfPlan::B1) % 4) == WO) {
                 constexpr int i = (t - GfPlan::B1) / 4;
                 if constexpr (i == 0) {
-                    if constexpr (!(ABL & 16)) issue_am((j + 3) >> 2, am_now, dc);
+                    issue_am((j + 3) >> 2, am_now, dc);
                 } else if constexpr (i == 1) {
-                    if constexpr (!(ABL & 16)) issue_raw(I0{}, Nn, rb3, dc);
+                    issue_raw(I0{}, Nn, rb3, dc);
                 } else if constexpr (i == 2) {
-                    if constexpr (!(ABL & 16)) issue_raw(I1{}, Nn, rb3, dc);
+                    issue_raw(I1{}, Nn, rb3, dc);
                 } else {
                     issue_a(std::integral_constant<int, (i - 3) % FM>{}, C, kb2, dc);
                 }
             }
             // decode: raw reads
-            if constexpr (!(ABL & 32)) {
-                if constexpr (t == GfPlan::B2) read_rwA(PC{}, tcl(j + 2));
-                if constexpr (t == GfPlan::RWB) read_rwB(PN_{});
-            }
+            if constexpr (t == GfPlan::B2) read_rwA(PC{}, tcl(j + 2));
+            if constexpr (t == GfPlan::RWB) read_rwB(PN_{});
             // decode: units.  Slots >= R0: tile j+2 (parity C, stage C); slots below: tile j+1 (parity Nn, stage Nn), whose
             // unit u sits at lookup_slot(u) - 128.
             {

@@ -1,5 +1,6 @@
 // gemm_fused4.hip — launch of k_gemm_fused4 (gemm_fused4.h): the fused 4-bit decode + MFMA GEMM on the four-wave pipeline, for
 // large M at blocksize 64.  Own translation unit (the kernel compiles for minutes).
+#include "dispatch.h"
 #include "gemm_fused4.h"
 
 namespace mbnb {

@@ -26,13 +26,6 @@
 
 namespace mbnb {
 
-#ifndef GI8_EPI_PARTS
-#define GI8_EPI_PARTS 4   // parts the 16-bit epilogue stores the wave's 128 rows in (4: 32 rows each)
-#endif
-#ifdef GI8_STAMPS     // diagnostic builds (tools/exp/i8_stamps.hip): cycles of the k-loop of workgroup 17's four waves
-__device__ unsigned long long g_gi8_stamps[8 + 4 * 256];
-#endif
-
 constexpr int GD_B1 = 36, GD_D0 = 36, GD_B2 = 100, GD_R0 = 100;   // slot plan of k_gemm_dense (GdPlan<8>)
 
 typedef int v2i_t __attribute__((ext_vector_type(2)));
@@ -46,9 +39,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave >> 1, wm = wave & 1;
-#ifdef GI8_STAMPS
-    if (tid == 0) g_gi8_stamps[8 + 4 * blockIdx.x + 0] = wall_clock64();
-#endif
 
     // tile -> workgroup: the walk of k_gemm_dense (gemm_dense.h, round 4): pseudo-patches of 32 tiles dealt to the XCDs in turn, 4 x 8 patches
     // that are ragged at the grid's edges (round 3 fell back to a column-major order whenever tiles_m % 4 or tiles_n % 8 was not 0)
@@ -77,10 +67,10 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
 #pragma unroll
     for (int pl = 0; pl < 8; pl++) {
         const int row = 8 * (8 * wave + pl) + (lane >> 3);
-        voff_a[pl] = (int)(row * K) + 16 * ((lane & 7) ^ ((row >> 1) & 7)) - GD_M0_GROUP * (pl & 3) * 1024;
+        voff_a[pl] = (int)(row * K) + 16 * ((lane & 7) ^ ((row >> 1) & 7)) - (pl & 3) * 1024;
         const int krow = 32 * wave + 4 * pl + (lane >> 4);
         const int c = (lane & 15) ^ (((krow & 7) << 1) | ((krow >> 4) & 1));
-        voff_b[pl] = (n0 + 16 * c < N ? (int)(krow * N) + 16 * c : 0x7FFF0000) - GD_M0_GROUP * (pl & 3) * 1024;
+        voff_b[pl] = (n0 + 16 * c < N ? (int)(krow * N) + 16 * c : 0x7FFF0000) - (pl & 3) * 1024;
     }
     const int kstep_b = (int)(128 * N);     // bytes of B between two k-steps
     const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)smem;
@@ -104,8 +94,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
         const i32x4_t rs = (q < 8) ? c.ra : c.rb;
         const int soff = (q < 8) ? (t << 7) : t * c.ksb;
         // four pieces share ONE M0 write: the instruction offset (added to the LDS address and to the global address alike) carries the
-        // piece inside the group, the per-lane offsets are that much smaller (gemm_dense.h, GD_M0_GROUP; launcher: K >= 256, N >= 256)
-        if constexpr (GD_M0_GROUP && (pl & 3) != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(soff), "n"((pl & 3) * 1024) : "memory", "m0");
+        // piece inside the group, the per-lane offsets are that much smaller (gemm_dense.h; launcher: K >= 256, N >= 256)
+        if constexpr ((pl & 3) != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(soff), "n"((pl & 3) * 1024) : "memory", "m0");
         else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(vo), "s"(rs), "s"(soff) : "memory", "m0");
     };
 
@@ -186,24 +176,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
         }
         if (j < nk) kstep(std::integral_constant<int, 1>{}, std::false_type{}, wo, j, dc);
     };
-#ifdef GI8_STAMPS
-    uint64_t gi_t0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gi_t0) :: "memory");
-    const unsigned long long gi_r1 = wall_clock64();
-#endif
     if (wave == 0) main_loop(std::integral_constant<int, 0>{});
     else if (wave == 1) main_loop(std::integral_constant<int, 1>{});
     else if (wave == 2) main_loop(std::integral_constant<int, 2>{});
     else main_loop(std::integral_constant<int, 3>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef GI8_STAMPS
-    {
-        uint64_t gi_t1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gi_t1) :: "memory");
-        if (blockIdx.x == 17 && (threadIdx.x & 63) == 0) g_gi8_stamps[threadIdx.x >> 6] = gi_t1 - gi_t0;
-        if (threadIdx.x == 0) { g_gi8_stamps[8 + 4 * blockIdx.x + 1] = gi_r1; g_gi8_stamps[8 + 4 * blockIdx.x + 2] = wall_clock64(); }
-    }
-#endif
 
     // ---- epilogue: acc[f][g][r] = sum for out[m0 + 128 wm + 16 g + (lane & 15)][n0 + 128 wn + 16 f + 4 (lane >> 4) + r]
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -260,8 +237,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
         }
         // Round 3: the wave's 128 rows go out in FOUR parts of 32 (two fragments) instead of two of 64 -- the stores of part q are in flight
         // while part q + 1 is read, converted and scaled (4.5 VALU per output: at two parts the epilogue took 8.8 us where the bf16 GEMM's
-        // takes 6, tools/exp/i8_stamps.py) --, and the two scale products are packed pairs (v_pk_mul_f32: two IEEE products, the same bits).
-        constexpr int NQ = GI8_EPI_PARTS, GQ = 8 / NQ;   // parts, fragments of 16 rows per part
+        // takes 6) --, and the two scale products are packed pairs (v_pk_mul_f32: two IEEE products, the same bits).
+        constexpr int NQ = 4, GQ = 8 / NQ;   // parts, fragments of 16 rows per part
         gd_static_for<NQ>([&](auto hh) {
             constexpr int H = decltype(hh)::value;
             const int64_t m_base = m0 + wm * 128 + 16 * GQ * H;
@@ -317,10 +294,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8_inplace(const int8_t *__rest
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         });
     }
-#ifdef GI8_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) g_gi8_stamps[8 + 4 * blockIdx.x + 3] = wall_clock64();
-#endif
 }
 
 }  // namespace mbnb

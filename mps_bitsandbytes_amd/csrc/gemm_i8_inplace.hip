@@ -1,5 +1,6 @@
 // gemm_i8_inplace.hip — launch of k_gemm_i8_inplace (gemm_i8_inplace.h): matmul_int8 for large aligned problems on the four-wave
 // pipeline with B read where it lies ([K, N], transposing LDS reads): no transpose pass, no workspace.
+#include "dispatch.h"
 #include "gemm_i8_inplace.h"
 
 namespace mbnb {

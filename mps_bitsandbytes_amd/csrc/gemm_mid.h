@@ -13,7 +13,7 @@
 // The k_gemm256s pipeline at a smaller scale, every global access in the loop an LDS-DMA with hand-counted vmcnt:
 //   * activations: 16 pieces of 8 rows x 128 B per k-step (2 per wave) into a ring of THREE 16 KiB stages, issued two
 //     k-steps ahead (a ring of five, issued four ahead, was slower: the k-step is bound by its LDS reads and its barrier,
-//     not by the L2 round trip -- tools/exp/abl_mid.py); the bank swizzle chunk ^ ((row >> 1) & 7) is applied to the
+//     not by the L2 round trip -- profiles/r02_mid_ablation.txt); the bank swizzle chunk ^ ((row >> 1) & 7) is applied to the
 //     source address;
 //   * packed weights two k-steps at a time: half a piece per wave = its own 8 rows x 64 B (whole 64-byte sectors) into one
 //     of two 4 KiB slots; a thread later picks the dword (8 k) of its (row, eighth) with one ds_read_b32;
@@ -37,7 +37,7 @@ constexpr int MID_RAW = MID_B + 2 * MID_B_STAGE, MID_RAW_SLOT = 4096;      // 2 
 constexpr int MID_AM = MID_RAW + 2 * MID_RAW_SLOT, MID_AM_SLOT = 1024;     // 2 absmax-by-4 slots
 constexpr int MID_LDS = MID_AM + 2 * MID_AM_SLOT;
 
-template <typename T, bool NESTED, int ABL = 0>   // ABL: timing-only diagnostic variants (tools/exp), 0 in the product
+template <typename T, bool NESTED>
 __global__ __launch_bounds__(512, 4) void k_gemm_mid(const T *__restrict__ X, typename Q4ProducerRT<T, NESTED>::Params wp,
                                                      const T *__restrict__ bias, void *__restrict__ out_v, int out_dtype,
                                                      float *__restrict__ partial, int64_t M, int64_t N, int64_t K,
@@ -232,33 +232,23 @@ __global__ __launch_bounds__(512, 4) void k_gemm_mid(const T *__restrict__ X, ty
         am_next = load_am(t2);
         const bool raw_now = (j & 1) == 0, am_now = (j & 3) == 0;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 1)) issue_a(j + MID_NA - 1, 0);
+        issue_a(j + MID_NA - 1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 2)) {
-            acc = Mfma<T>::run(wf[0], xf[0], acc);
-            acc = Mfma<T>::run(wf[1], xf[1], acc);
-        } else {
-            asm volatile("" ::"v"(wf[0]), "v"(xf[0]), "v"(wf[1]), "v"(xf[1]));
-        }
+        acc = Mfma<T>::run(wf[0], xf[0], acc);
+        acc = Mfma<T>::run(wf[1], xf[1], acc);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 1)) issue_a(j + MID_NA - 1, 1);
+        issue_a(j + MID_NA - 1, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 4)) finish4(L0, am_cur, Nn);
-        else asm volatile("" ::"v"(L0[0]), "v"(L0[7]), "v"(am_cur));
-        if constexpr (!(ABL & 2)) acc = Mfma<T>::run(wf[2], xf[2], acc);
-        else asm volatile("" ::"v"(wf[2]), "v"(xf[2]));
+        finish4(L0, am_cur, Nn);
+        acc = Mfma<T>::run(wf[2], xf[2], acc);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 8)) {
-            if (raw_now) issue_raw2((j + 4) >> 1);
-            if (am_now) issue_am4((j + 4) >> 2);
-        }
+        if (raw_now) issue_raw2((j + 4) >> 1);
+        if (am_now) issue_am4((j + 4) >> 2);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 2)) acc = Mfma<T>::run(wf[3], xf[3], acc);
-        else asm volatile("" ::"v"(wf[3]), "v"(xf[3]));
+        acc = Mfma<T>::run(wf[3], xf[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         // A(j+1) and everything else issued in earlier steps has landed once only this step's issues are outstanding
-        if constexpr (ABL & 9) { MBNB_VMCNT(0); }
-        else if (am_now) { if constexpr (NESTED) MBNB_VMCNT(5); else MBNB_VMCNT(4); }
+        if (am_now) { if constexpr (NESTED) MBNB_VMCNT(5); else MBNB_VMCNT(4); }
         else if (raw_now) MBNB_VMCNT(3);
         else MBNB_VMCNT(2);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

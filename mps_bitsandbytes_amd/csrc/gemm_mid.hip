@@ -1,4 +1,5 @@
 // gemm_mid.hip — launcher of k_gemm_mid (gemm_mid.h): the mid-sized-batch fused 4-bit GEMM, with its split-K policy.
+#include "dispatch.h"
 #include "gemm_mid.h"
 
 namespace mbnb {
@@ -33,10 +34,10 @@ int64_t gemm_mid_workspace_bytes(int64_t M, int64_t N, int64_t K) {
     return s > 1 ? s * M * N * 4 : 0;
 }
 
-template <typename T, typename OutT, bool NESTED, int ABL = 0>
+template <typename T, typename OutT, bool NESTED>
 int launch_gemm_mid(const T *x, const typename Q4ProducerRT<T, NESTED>::Params &wp, const T *bias, OutT *out, int64_t M,
                     int64_t N, int64_t K, float *ws, int64_t ws_bytes, int force_slices, hipStream_t st) {
-    auto kern = k_gemm_mid<T, NESTED, ABL>;
+    auto kern = k_gemm_mid<T, NESTED>;
     if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), MID_LDS, "matmul_4bit(mid)")) return rc;
     int64_t slices = force_slices > 0 ? force_slices : gemm_mid_slices(M, N, K);
     if (slices > 1 && (ws == nullptr || ws_bytes < slices * M * N * 4 || (reinterpret_cast<uintptr_t>(ws) & 15))) slices = 1;

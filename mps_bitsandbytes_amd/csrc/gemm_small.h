@@ -35,18 +35,6 @@ template <int N, class F> __device__ __forceinline__ void gs_static_for(F &&f) {
 }
 
 template <int MF> constexpr int gemm_small_lds_bytes() { return 2 * 16 * MF * 512; }
-#ifndef GS_PK_MUL
-#define GS_PK_MUL 0  // 1 (diagnostic builds): one v_pk_mul_f32 per decoded byte instead of two v_mul_f32 -- same bits, SLOWER (27.9 -> 29.0 us at 512 x 4096^2, profiles/r03_small_pk_mul_ab.txt)
-#endif
-#ifndef GS_ABL
-#define GS_ABL 0     // diagnostic builds (tools/exp/small_stamps.hip): 1 no LDS-DMA pieces in the steps, 2 no decode, 4 no fragment reads (timing only)
-#endif
-#ifdef GS_STAMPS
-__device__ unsigned long long g_gs_stamps[256];      // diagnostic builds (tools/exp/small_stamps.hip): cycle stamps of one wave's steps
-#ifndef GS_STAMP_TID
-#define GS_STAMP_TID 0
-#endif
-#endif
 
 // MAXS_: steps of a slice whose weights the prologue loads into registers (12 registers per step and fragment); 0 = 8 (NF = 1) / 4
 // (NF = 2).  16 (round 3): K = 4096 in ONE slice -- 384 < M <= 512 rows on a 4096-wide layer are 256 workgroups in one round with
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
 #pragma unroll
     for (int i = 0; i < NPW; i++) {
         const int row = 2 * (NPW * wave + i) + (lane >> 5), pos = lane & 31;
-        voff[i] = (int)(row * K * 2) + 16 * ((pos & 16) | ((pos & 15) ^ swz(row & 15))) - GD_M0_GROUP * (i & 3) * 1024;
+        voff[i] = (int)(row * K * 2) + 16 * ((pos & 16) | ((pos & 15) ^ swz(row & 15))) - (i & 3) * 1024;
     }
     const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)smem;
     const uint32_t lds_wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(smem_base + (uint32_t)(wave * NPW * 1024)));
@@ -109,8 +97,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
         const int vo = voff[i];
         const i32x4_t rs = rs_a;
         // four pieces share ONE M0 write: the instruction offset (added to the LDS address and to the global address alike) carries the
-        // piece inside the group, the per-lane offsets are that much smaller (gemm_dense.h, GD_M0_GROUP; K >= 512 here)
-        if constexpr (GD_M0_GROUP && (i & 3) != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(soff), "n"((i & 3) * 1024) : "memory", "m0");
+        // piece inside the group, the per-lane offsets are that much smaller (gemm_dense.h; K >= 512 here)
+        if constexpr ((i & 3) != 0) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" ::"v"(vo), "s"(rs), "s"(soff), "n"((i & 3) * 1024) : "memory", "m0");
         else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(vo), "s"(rs), "s"(soff) : "memory", "m0");
     };
     auto issue_a = [&](int stage, int step) __attribute__((always_inline)) {
@@ -182,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
     // newest NW operations -- leaves it in flight for a whole step; it has landed by the wait of step t + 2 (in-order counter), one step
     // before its first use (the tail of step t + 2 looks the first two slices of step t + 3 up, below), where the registers are passed
     // through an empty asm.  (Until then ALL steps of the slice were requested and awaited here: 128 KiB per workgroup at 16 steps, 33.5 MB
-    // over the grid of a 512 x 4096 x 4096 call -- 10 of its 35 us went by before the first MFMA, tools/exp/small_stamps.py.)  The steps
+    // over the grid of a 512 x 4096 x 4096 call -- 10 of its 35 us went by before the first MFMA, profiles/r03_small_weight_streaming.txt.)  The steps
     // are fully unrolled, so every step's registers are their own: no ring, no copies.
     constexpr int NW = NF * 2 * (NESTED ? 3 : 2);     // vector-memory instructions of one step's weight request
     constexpr int PD = 3;
@@ -223,7 +211,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
     // (independent VALU work the matrix pipe runs beside).  Round 3: the pipeline runs ACROSS the step boundary -- the lookups of the
     // next step's slices 0 and 1 and the products of its slice 0 need only that step's weights (registers), so they ride in the last two
     // slices of this step; behind the barrier only the activation fragments of slice 0 are waited for (each step used to start with
-    // lookup -> products -> fragment reads -> first MFMA in series: ~550 of its ~2800 cycles, small_stamps.py with GS_ABL = 7).
+    // lookup -> products -> fragment reads -> first MFMA in series: ~550 of its ~2800 cycles).
     // next >= 0: the LDS-DMA pieces of step `next` go out into the other stage from INSIDE the step, NPW / 8 per slice behind that
     // slice's MFMAs (all of them up front cost the wave ~16 x 80 issue cycles before its first MFMA: 2.4 -> 1.x us per step)
     const char *lut2 = reinterpret_cast<const char *>(s_lut2);
@@ -245,19 +233,13 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
             u32x4 o;
 #pragma unroll
             for (int b = 0; b < 4; b++) {
-#if GS_PK_MUL
-                // both products of a byte's pair in one v_pk_mul_f32 (two IEEE products: the same bits)
-                f32x2 pr;
-                const f32x2 sc2 = f32x2{ra[f][j], ra[f][j]};
-                asm("v_pk_mul_f32 %0, %1, %2" : "=v"(pr) : "v"(src[f][b]), "v"(sc2));
-                o[b] = pack2<T>(pr[0], pr[1]);
-#else
+                // two v_mul_f32: one v_pk_mul_f32 per byte gives the same bits but is SLOWER (27.9 -> 29.0 us at 512 x 4096^2,
+                // profiles/r03_small_pk_mul_ab.txt)
                 float p0, p1;
                 const float l0 = src[f][b][0], l1 = src[f][b][1], sc = ra[f][j];
                 asm("v_mul_f32 %0, %1, %2" : "=v"(p0) : "v"(l0), "v"(sc));
                 asm("v_mul_f32 %0, %1, %2" : "=v"(p1) : "v"(l1), "v"(sc));
                 o[b] = pack2<T>(p0, p1);
-#endif
             }
             wf[f] = __builtin_bit_cast(Frag, o);
         });
@@ -289,15 +271,15 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
         }
         gs_static_for<8>([&](auto ii) {
             constexpr int i = decltype(ii)::value, P = i & 1;
-            if constexpr (i < 7 && !(GS_ABL & 4)) issue_x(std::integral_constant<int, (i + 1) & 7>{}, std::integral_constant<int, P ^ 1>{});
-            if constexpr (i < 7 && !(GS_ABL & 2)) finish(lk[P ^ 1], ra, std::integral_constant<int, (i + 1) & 7>{}, wn);
-            if constexpr (i < 6 && !(GS_ABL & 2)) lookup(w, std::integral_constant<int, (i + 2) & 7>{}, lk[P]);
-            if constexpr (i >= 6 && HAS_NX && !(GS_ABL & 2)) lookup(wnx, std::integral_constant<int, i - 6>{}, lk[P]);      // slices 0, 1 of the next step
+            if constexpr (i < 7) issue_x(std::integral_constant<int, (i + 1) & 7>{}, std::integral_constant<int, P ^ 1>{});
+            if constexpr (i < 7) finish(lk[P ^ 1], ra, std::integral_constant<int, (i + 1) & 7>{}, wn);
+            if constexpr (i < 6) lookup(w, std::integral_constant<int, (i + 2) & 7>{}, lk[P]);
+            if constexpr (i >= 6 && HAS_NX) lookup(wnx, std::integral_constant<int, i - 6>{}, lk[P]);      // slices 0, 1 of the next step
 #pragma unroll
             for (int f = 0; f < NF; f++)
 #pragma unroll
                 for (int g = 0; g < MF; g++) acc[f][g] = Mfma16<T>::run(wf[f], xf[P][g], acc[f][g]);
-            if (next >= 0 && !(GS_ABL & 1)) {
+            if (next >= 0) {
                 gs_static_for<NPW / 8>([&](auto pp) { issue_piece(std::integral_constant<int, i * (NPW / 8) + decltype(pp)::value>{}, stage ^ 1, nsoff); });
             }
             if constexpr (i < 7) {
@@ -318,14 +300,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
     // step t: activations in stage t & 1 (A(t+1) goes out during step t, behind the barrier that frees its stage), weights in wr[t]
     auto step = [&](auto tt) __attribute__((always_inline)) {
         constexpr int TT = decltype(tt)::value;
-#ifdef GS_STAMPS
-        const uint64_t ta = __builtin_readcyclecounter();
-#endif
         // the newest weight request -- step TT + 2's, issued at the end of step TT - 1 (step 2's by the prologue) -- stays in flight
         wait_but_newest(TT + 2 < nsteps);
-#ifdef GS_STAMPS
-        const uint64_t tw = __builtin_readcyclecounter();
-#endif
         if constexpr (TT == 0) {
             // the first step's slices 0 and 1 enter the pipeline here (the byte table is visible behind this barrier)
             landed(wr[0]);
@@ -341,19 +317,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_small(const T *__restrict__ X, 
             __syncthreads();        // A(t) visible; every wave is done reading the other stage (step t - 1)
             if constexpr (TT + 1 < MAXS) landed(wr[TT + 1]);
         }
-#ifdef GS_STAMPS
-        const uint64_t tb = __builtin_readcyclecounter();
-#endif
         constexpr int NX = TT + 1 < MAXS ? TT + 1 : TT;
         compute(TT & 1, wr[TT], wr[NX], std::integral_constant<bool, (TT + 1 < MAXS)>{}, TT + 1 < nsteps ? TT + 1 : -1);
         if constexpr (TT + PD < MAXS) {
             if (TT + PD < nsteps) load_w(TT + PD, wr[TT + PD]);
         }
-#ifdef GS_STAMPS
-        if (tid == GS_STAMP_TID && blockIdx.x == 7 && blockIdx.y == 0 && blockIdx.z == 0) {
-            g_gs_stamps[4 * TT + 0] = ta; g_gs_stamps[4 * TT + 1] = tw; g_gs_stamps[4 * TT + 2] = tb; g_gs_stamps[4 * TT + 3] = __builtin_readcyclecounter();
-        }
-#endif
     };
     gs_static_for<MAXS>([&](auto tt) {
         if (decltype(tt)::value < nsteps) step(tt);

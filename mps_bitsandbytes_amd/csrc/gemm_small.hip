@@ -1,4 +1,5 @@
 // gemm_small.hip — launch of k_gemm_small (gemm_small.h): fused 4-bit GEMM for 16/32 < M <= 256 rows, blocksize >= 32.
+#include "dispatch.h"
 #include "gemm_small.h"
 #include "gemm_mid.h"
 
@@ -19,7 +20,7 @@ bool gemm_small8_shape(int64_t M, int64_t N, int64_t K) { return small_shape_up_
 // about  0.4 us + its activation KiB / 55 GB/s  (small_check.py: 64 KiB -> 1.6 us, 32 KiB -> 1.0 us), a slice pays a prologue
 // of ~2.5 us, and every extra slice adds M x N x 4 bytes of partials written and read (6 TB/s).
 struct SmallPlan { int nf; int64_t slices; double us; int mf; };
-// Round 3 (after the weights streamed in and the pipeline crossed the step boundary; tools/exp/small_stamps.py, small_nf2.py): a step of the 64-row
+// Round 3 (after the weights streamed in and the pipeline crossed the step boundary; cycle stamps): a step of the 64-row
 // form (NF = 1, 64 MFMAs per wave) takes ~3400 cycles = 1.5-1.6 us whatever the slice length, a step of the 128-row form (NF = 2, 128 MFMAs) ~4760 =
 // 2.1 us with half the CUs busy and ~3.0 us with all of them (512 x 8192 x 4096: 50.8 us) -- 10-30 % less per weight row, because the activation tile (the
 // CU's inflow limit) is taken in once for twice the rows.  The 128-row form
@@ -31,7 +32,7 @@ SmallPlan gemm_small_plan(int64_t M, int64_t N, int64_t K, int maxs_mf8 = 16) {
     // Tile heights.  Up to 64 rows: 64 (MF = 4).  Above 256 rows: 128 (MF = 8; NF = 2 there, k_gemm_small<.., 8, 2, 16>).  In between both
     // are tried (the 4-bit kernel only: maxs_mf8 == 16): 64-row tiles double the workgroups, which often saves the K split and its reduction
     // launch -- 256 x 4096^2: 256 workgroups x 16 steps in ONE slice 18.0 us against 128 x 2 slices + reduction 22.4
-    // (tools/exp/ab_small_pk.py, ab_small_mf.py).
+    // (tools/exp/ab_small_mf.py, profiles/r03_small_tile_height_ab.txt).
     const int mf_lo = M > 64 && (M > 256 || maxs_mf8 != 16) ? 8 : 4, mf_hi = M > 64 ? 8 : 4;
     for (int mf = mf_lo; mf <= mf_hi; mf += 4) {
         const int64_t mt = (M + 16 * mf - 1) / (16 * mf);

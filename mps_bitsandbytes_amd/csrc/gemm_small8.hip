@@ -1,11 +1,9 @@
 // gemm_small8.hip — launch of k_gemm_small8 (gemm_small8.h): W8A16 (int8 / FP8 weights) for 16/32 < M <= 256 rows.
+#include "dispatch.h"
 #include "gemm_small8.h"
 #include "gemm_mid.h"
 
 namespace mbnb {
-
-bool gemm_small8_shape(int64_t M, int64_t N, int64_t K);
-int64_t gemm_small8_slices(int64_t M, int64_t N, int64_t K);
 
 // Returns MBNB_NOT_APPLICABLE when the kernel cannot serve the call.
 template <typename T, int WF>

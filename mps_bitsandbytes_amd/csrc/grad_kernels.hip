@@ -4,13 +4,9 @@
 // weight Wt [K, N] in the weight dtype (k_dequant_t), then runs the forward's dense GEMM with A = dY, weight = Wt, ldw = N and the
 // library's own plan (gemm_dense.hip).  k_grad_generic decodes W on the fly and serves everything the dense path does not.
 #include "common.h"
+#include "dispatch.h"
 
 namespace mbnb {
-
-int64_t gemm_dense_slices(int64_t, int64_t, int64_t);
-int64_t gemm_dense_wd_bytes(int64_t, int64_t);
-int gemm_dense_direct(const void *, const void *, int, const void *, int, void *, int64_t, int64_t, int64_t, int64_t, float *, int64_t, int, int,
-                      hipStream_t);
 
 // =====================================================================================
 // Transposed dequantise pass.  A lane decodes an 8 x 8 block -- 8 consecutive rows n of W, 8 consecutive columns k -- into 32 pair words

@@ -4,6 +4,7 @@
 //                (reference: functional.py:788-793; Metal kernel int8_matmul_dequant mm:155-196)
 //   linear_int8  16-bit activations x int8 weights decoded in the B-tile producer (gemm_tile.h)
 //                (reference: Linear8bit.forward nn/linear8bit.py:70-102; Metal int8_matmul_simd mm:203-305)
+#include "dispatch.h"
 #include "gemm256.h"
 #include "gemm256w.h"
 
@@ -463,17 +464,10 @@ __global__ __launch_bounds__(256) void k_matmul_i8_generic_nt(const int8_t *__re
     out[i] = from_f32<OutT>((float)acc * (sA[m] / 127.0f) * (sB[n] / 127.0f));
 }
 
-// gemm_dense.hip: the four-wave pipeline on int8 operands (ep: OutlierAwareLinear's second term and bias in its epilogue)
-bool gemm_i8_dense_shape(int64_t M, int64_t N, int64_t K);
-bool gemm_i8_dense_outlier_ok(const OutlierEpilogue &ep, int out_dtype);
-int launch_gemm_i8_dense(const int8_t *, const int8_t *, const float *, const float *, int64_t, int64_t, int64_t, int, void *, hipStream_t,
-                         const OutlierEpilogue *ep = nullptr);
-
 // `ep` (may be nullptr): outlier / bias epilogue.  It is applied only by the 256 x 256 kernels with a 16-bit output;
 // *ep_done tells the caller whether it was (otherwise the caller runs k_outlier_add afterwards).
 int matmul_int8_nt_dispatch(const int8_t *A, const int8_t *Bt, const float *sA, const float *sB, int64_t M, int64_t N,
-                            int64_t K, int out_dtype, void *out, hipStream_t st, const OutlierEpilogue *ep = nullptr,
-                            bool *ep_done = nullptr) {
+                            int64_t K, int out_dtype, void *out, hipStream_t st, const OutlierEpilogue *ep, bool *ep_done) {
     if (ep_done) *ep_done = false;
     const bool fast = (K % 16 == 0) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bt)) & 15) == 0;
     if (!fast) {
@@ -535,8 +529,6 @@ int matmul_int8_nt_dispatch(const int8_t *A, const int8_t *Bt, const float *sA, 
     return check_launch("matmul_int8(mfma)");
 }
 
-bool gemm_i8_inplace_shape(const int8_t *, const int8_t *, int64_t, int64_t, int64_t);
-int launch_gemm_i8_inplace(const int8_t *, const int8_t *, const float *, const float *, int64_t, int64_t, int64_t, int, void *, hipStream_t);
 // matmul_int8 reads B as the reference passes it, [K, N] row-major.  Large aligned problems go straight to the 256 x 256
 // kernel's transposing-read form (no workspace); everything else is first re-laid out K-contiguous into the caller's
 // workspace (N * K bytes) or, without one, served by the generic kernel.
@@ -713,11 +705,6 @@ __global__ __launch_bounds__(1024) void k_skinny8(const T *__restrict__ X, const
     }
 }
 
-int64_t matmul4_splitk_slices(int64_t M, int64_t N, int64_t K);
-
-template <typename T, int WF>
-int launch_gemm_small8(const T *, const uint8_t *, const float *, const T *, T *, int64_t, int64_t, int64_t, float *, int64_t, hipStream_t);
-
 template <typename T, int WF = W8_INT8>
 static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t *W, const float *scales, int64_t N,
                               const void *bias, void *out, float *ws, int64_t ws_bytes, hipStream_t st) {
@@ -790,9 +777,6 @@ static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t 
     set_kernel_name(WF == W8_INT8 ? "w8a16_generic" : "fp8a16_generic");
     return check_launch("linear_int8(generic)");
 }
-
-int linear8_dense_path(const void *, int, int64_t, int64_t, const void *, const float *, int64_t, bool, const void *, void *, void *, int64_t,
-                       hipStream_t);
 
 int linear_int8_dispatch(const void *X, int dtype, int64_t M, int64_t K, const int8_t *W, const float *scales,
                          int64_t N, const void *bias, void *out, void *workspace, int64_t ws_bytes, bool fused_only, hipStream_t st) {

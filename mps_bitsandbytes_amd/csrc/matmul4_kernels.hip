@@ -14,27 +14,12 @@
 #include <type_traits>
 #include <utility>
 
+#include "dispatch.h"
 #include "gemm256.h"
 #include "gemv4.h"
 #include "gemv4_lean.h"
 
 namespace mbnb {
-
-// mid-sized batches (gemm_mid.h), compiled in gemm_mid.hip
-template <typename T, typename OutT, bool NESTED, int ABL = 0>
-int launch_gemm_mid(const T *x, const typename Q4ProducerRT<T, NESTED>::Params &wp, const T *bias, OutT *out, int64_t M,
-                    int64_t N, int64_t K, float *ws, int64_t ws_bytes, int force_slices, hipStream_t st);
-bool gemm_mid_shape(int64_t M, int64_t N, int64_t K);
-bool gemm_small_shape(int64_t M, int64_t N, int64_t K, int64_t K_weight);
-bool gemm_small_one_round(int64_t M, int64_t N, int64_t K, int64_t K_weight, int64_t ws_bytes);
-template <typename T, typename OutT, bool NESTED>
-int launch_gemm_small(const T *, const uint8_t *, const AbsmaxView &, const T *, OutT *, int64_t, int64_t, int64_t, int64_t, int, int, float *,
-                      int64_t, hipStream_t);
-int matmul_4bit_fused4_path(const void *, int64_t, int64_t, const uint8_t *, const AbsmaxView &, int64_t, int64_t, int, int, int, const void *, int, void *,
-                            hipStream_t);
-int matmul_4bit_f32_path(const void *, int64_t, int64_t, const uint8_t *, const AbsmaxView &, int64_t, int64_t, int, int, const void *, int, void *, void *, int64_t, hipStream_t);
-int matmul_4bit_dense_path(const void *, int64_t, int64_t, const uint8_t *, const AbsmaxView &, int64_t, int64_t, int, int, int, const void *,
-                           int, void *, void *, int64_t, hipStream_t);
 
 // =====================================================================================
 // generic kernel: wave per (n, m-chunk of MT rows); lanes stride over k in steps of 8

@@ -8,14 +8,9 @@
 //
 // The int8 contraction itself is the MFMA kernel of int8_kernels.hip (matmul_int8_nt_dispatch).
 #include "common.h"
+#include "dispatch.h"
 
 namespace mbnb {
-
-int check_launch(const char *what);
-void set_error(const char *fmt, ...);
-void set_kernel_name(const char *name);
-int matmul_int8_nt_dispatch(const int8_t *A, const int8_t *Bt, const float *sA, const float *sB, int64_t M, int64_t N,
-                            int64_t K, int out_dtype, void *out, hipStream_t st, const OutlierEpilogue *ep, bool *ep_done);
 
 // ------------------------------------------------------------------------------------ embeddings
 // One workgroup per looked-up row.  A thread decodes 4 packed bytes (8 values) per trip: u32 load, table

@@ -8,6 +8,7 @@
 // Compiled with -ffp-contract=off: every f32 operation below is a single IEEE operation in
 // the order the reference performs it (division, not reciprocal-multiply, for x / absmax).
 #include "common.h"
+#include "dispatch.h"
 
 namespace mbnb {
 
@@ -1122,9 +1123,6 @@ int dequantize_4bit_dispatch(const uint8_t *packed, const AbsmaxView &am, int64_
     }
 #undef MBNB_DQ
 }
-
-int quantize_rowwise_dispatch(const void *, int, int64_t, int64_t, int8_t *, float *, hipStream_t);
-int dequantize_rowwise_dispatch(const int8_t *, const float *, int64_t, int64_t, int, void *, hipStream_t, int store_policy = 0);
 
 int quantize_blockwise_dispatch(const void *A, int dtype, int64_t numel, int blocksize, const float *absmax_in,
                                 int8_t *out, float *absmax_out, hipStream_t st) {

@@ -1,6 +1,6 @@
-// m0_exp.hip — A/B harness for GD_M0_GROUP (common.h) in the kernels other than k_gemm_dense (dense_exp.hip): built twice into
-// libm0_exp0.so / libm0_exp1.so.  exp_d128 (k_gemm_dense128, bf16), exp_i8 (k_gemm_i8_inplace, bf16 out), exp_small (k_gemm_small<bf16, plain,
-// MF 8, NF 1, 16 steps>, one slice, no partials).
+// m0_exp.hip — direct launches of the library's pipelined kernels other than k_gemm_dense, built into libm0_exp.so (small_graph_vs_stream.py
+// loads it).  exp_d128 (k_gemm_dense128, bf16), exp_i8 (k_gemm_i8_inplace, bf16 out), exp_small (k_gemm_small<bf16, plain, MF 8, NF 1, 16 steps>,
+// one slice, no partials).
 #include "../../mps_bitsandbytes_amd/csrc/gemm_dense128.h"
 #include "../../mps_bitsandbytes_amd/csrc/gemm_i8_inplace.h"
 #include "../../mps_bitsandbytes_amd/csrc/gemm_small.h"

@@ -7,7 +7,7 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _native
 dev = torch.device("cuda:0")
 here = os.path.dirname(os.path.abspath(__file__))
-lib = ctypes.CDLL(os.path.join(here, "libm0_pk0.so"))
+lib = ctypes.CDLL(os.path.join(here, "libm0_exp.so"))
 I64, P = ctypes.c_int64, ctypes.c_void_p
 lib.exp_small_v.restype = ctypes.c_int; lib.exp_small_v.argtypes = [P] * 4 + [I64] * 3 + [P, ctypes.c_int]
 
