@@ -2,7 +2,7 @@
 """
 bench.py — throughput of the NF4 dequant + matmul hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: N child ranks are started)
+    python bench.py --gpus N --steps K --warmup W [--full]  (N > 1 without a launcher: N child ranks are started)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ Timing: a disclosed time-based pre-warm ("prewarm_ms": the clock nee
 W untimed warm-up steps, then R = 5 repetitions of the K-step loop, each bracketed by barrier + synchronize on both
 sides and reduced with MAX over ranks; `value` and `ms_per_step` come from the MEDIAN repetition, and the kernel's
 launch duration (`roofline.kernel_us`) from HIP events recorded inside that same repetition on the launching stream.
+
+A plain run does only what the headline needs: set up, pre-warm, warm up, time the repetitions, dump (--dump-outputs) and
+print the line.  Everything that takes runs of its own -- the dominant kernel alone, `no_prewarm`, `cpu_baseline`, `gemv`,
+`batch_sweep`, `roofline.empirical` / `ceiling`, the `secondary` lines and, with N > 1, the other gather curves -- is
+measured only with --full (the --no-* switches then leave parts of it out).
 
 One "step" = one pass of the hot path over one batch: Linear4bit-style matmul_4bit on an NF4 weight
 4096x4096 (bf16-origin, blocksize 64), M = 4096 rows per GPU, bf16 activations, inputs resident in HBM.  At this M the
@@ -20,7 +25,8 @@ all-gather of the output shards over xGMI (weak scaling).
 
 Rank 0 prints ONE JSON line: metric/value per the driver contract plus
   "roofline"     the OPERATION (the whole step, every launch of one matmul call; MFMA-bound): algorithmic flops / step duration
-                 measured with HIP events on the launching stream; `dominant_kernel` carries the largest launch alone
+                 measured with HIP events on the launching stream; with --full, `dominant_kernel` carries the largest launch alone
+and, with --full only:
   "cpu_baseline" the CPU oracle (a port of the reference's CPU path) timed on this box's host
                  cores on a bounded row-sample of the same workload
   "gemv"         the M = 1 decode shape of the metric (HBM-bound), rotating over 64 distinct
@@ -31,7 +37,9 @@ Rank 0 prints ONE JSON line: metric/value per the driver contract plus
 
 --dump-outputs DIR writes what the last timed step returned (for every workload the line times) as DIR/<workload>.npy in
 float32, outputs above DUMP_MAX_ELEMS as a fixed, seeded sample of whole rows; the inputs are seeded, so two builds can be
-compared output for output.
+compared output for output.  A plain run of the default workload (N = 1) writes the secondary workloads' arrays as well, each
+from one untimed step on the same inputs: the kernels are deterministic, so these are the bits a --full run's last timed step
+returns, and both forms write the same files.
 """
 import argparse
 import json
@@ -64,7 +72,10 @@ def parse():
                     "with --no-gather and the default these are the three curves of SURVEY 8e")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemv", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="default workload at N = 1: skip the secondary lines (BASELINE configs 2, 3 and stand-alone 1)")
+    ap.add_argument("--no-secondary", action="store_true", help="default workload at N = 1: skip the secondary lines (BASELINE configs 2, 3 and stand-alone 1), "
+                    "and in a plain run their --dump-outputs arrays")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own beside the headline: dominant kernel, cold clock, "
+                    "CPU baselines, GEMV and batch sweep, empirical ceilings, secondary lines, the other gather curves (N > 1)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--prewarm-ms", type=float, default=400.0, help="untimed, time-based load before the warm-up steps")
     ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step loop; the median one is reported")
@@ -199,17 +210,18 @@ def bench_nn(args, wl, dev, bnb, synthetic, dumps):
         if args.dump_outputs:
             dumps[wl] = dump_sample(last)
         del last
-        kern_ms = event_time_ms(step, args.steps)
         nbytes = bytes_per_row * tokens
-        gbs = nbytes / (kern_ms * 1e-3) / 1e9
         out.update({"metric": f"effective GB/s, {label} lookup of {tokens} rows from a {num} x {dim} table -> bf16",
                     "value": round(nbytes / (elapsed / args.steps) / 1e9, 1), "unit": "GB/s",
                     "ms_per_step": round(elapsed / args.steps * 1e3, 5), "dtype": "u8" if wl == "embed4" else "int8",
                     "config": {"workload": f"{label}.forward, vocabulary {num}, embedding_dim {dim}, {tokens} indices per step",
-                               "algorithmic_bytes_per_row": bytes_per_row},
-                    "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                 "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None, "kernel_us": round(kern_ms * 1e3, 2)}})
-        if not args.no_cpu_baseline:
+                               "algorithmic_bytes_per_row": bytes_per_row}})
+        if args.full:
+            kern_ms = event_time_ms(step, args.steps)
+            gbs = nbytes / (kern_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                               "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None, "kernel_us": round(kern_ms * 1e3, 2)}
+        if args.full and not args.no_cpu_baseline:
             cpu()
             t0, n = time.perf_counter(), 0
             while time.perf_counter() - t0 < min(args.cpu_seconds, 5.0):
@@ -240,17 +252,18 @@ def bench_nn(args, wl, dev, bnb, synthetic, dumps):
         if args.dump_outputs:
             dumps[wl] = dump_sample(last)
         del last
-        kern_ms = event_time_ms(step, args.steps)
         flops = 2.0 * M * N * K
-        tf = flops / (kern_ms * 1e-3) / 1e12
         name = "Linear8bit (row-wise INT8 weights)" if wl == "w8a16" else "LinearFP8 (E4M3 weights, reference format)"
         out.update({"metric": f"effective bf16 TFLOPS, {name} forward 4096x4096 @ M=4096", "value": round(flops / (elapsed / args.steps) / 1e12, 1),
                     "unit": "TFLOP/s", "ms_per_step": round(elapsed / args.steps * 1e3, 5), "dtype": "bf16",
                     "config": {"workload": f"{name}.forward, bf16 activations, weights dequantised once into the workspace + k_gemm_dense at this M (fused W8A16 kernels below 512 rows)", "M": M, "N": N, "K": K,
-                               "kernel": __import__("mps_bitsandbytes_amd")._native.last_kernel()},
-                    "roofline": {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_TFLOPS["bf16"], "unit": "TFLOP/s",
-                                 "frac": round(tf / PEAK_TFLOPS["bf16"], 4), "traffic": None, "kernel_us": round(kern_ms * 1e3, 2)}})
-        if not args.no_cpu_baseline:
+                               "kernel": __import__("mps_bitsandbytes_amd")._native.last_kernel()}})
+        if args.full:
+            kern_ms = event_time_ms(step, args.steps)
+            tf = flops / (kern_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_TFLOPS["bf16"], "unit": "TFLOP/s",
+                               "frac": round(tf / PEAK_TFLOPS["bf16"], 4), "traffic": None, "kernel_us": round(kern_ms * 1e3, 2)}
+        if args.full and not args.no_cpu_baseline:
             rows = 256
             xs = x[:rows].cpu()
             if wl == "w8a16":
@@ -285,16 +298,17 @@ def bench_nn(args, wl, dev, bnb, synthetic, dumps):
     if args.dump_outputs:
         dumps[wl] = dump_sample(last)
     del last
-    kern_ms = event_time_ms(step, args.steps)
     ops = 2.0 * M * N * K
-    tops = ops / (kern_ms * 1e-3) / 1e12
     out.update({"metric": "effective TOP/s, OutlierAwareLinear.forward 4096x4096 @ M=4096 (row-wise int8 quantise + int8 MFMA + 16 outlier columns + bias)",
                 "value": round(ops / (elapsed / args.steps) / 1e12, 1), "unit": "TOP/s", "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-                "dtype": "int8", "config": {"workload": "OutlierAwareLinear.forward, fp16 activations, 16 outlier columns, bias", "M": M, "N": N, "K": K},
-                "roofline": {"bound": "mfma", "achieved": round(tops, 1), "peak": PEAK_TFLOPS["int8"], "unit": "TOP/s",
-                             "frac": round(tops / PEAK_TFLOPS["int8"], 4), "traffic": _outlier_traffic(), "kernel_us": round(kern_ms * 1e3, 2),
-                             "note": "whole forward (2 kernels: masked row-wise quantiser + int8 GEMM with the outlier term and bias in its epilogue) / int8 dense peak; traffic: PMC bytes of the GEMM launch (profiles/traffic.json)"}})
-    if not args.no_cpu_baseline:
+                "dtype": "int8", "config": {"workload": "OutlierAwareLinear.forward, fp16 activations, 16 outlier columns, bias", "M": M, "N": N, "K": K}})
+    if args.full:
+        kern_ms = event_time_ms(step, args.steps)
+        tops = ops / (kern_ms * 1e-3) / 1e12
+        out["roofline"] = {"bound": "mfma", "achieved": round(tops, 1), "peak": PEAK_TFLOPS["int8"], "unit": "TOP/s",
+                           "frac": round(tops / PEAK_TFLOPS["int8"], 4), "traffic": _outlier_traffic(), "kernel_us": round(kern_ms * 1e3, 2),
+                           "note": "whole forward (2 kernels: masked row-wise quantiser + int8 GEMM with the outlier term and bias in its epilogue) / int8 dense peak; traffic: PMC bytes of the GEMM launch (profiles/traffic.json)"}
+    if args.full and not args.no_cpu_baseline:
         rows = 256
         xs = x[:rows].cpu()
         q, sc, oi, ow, b = oa.weight_int8.cpu(), oa.weight_scales.cpu(), oa.outlier_indices.cpu(), oa.outlier_weights.cpu(), oa.bias.cpu()
@@ -475,8 +489,9 @@ def gen_normal(synthetic, shape, dt, seed, std, dev):
     return synthetic.normal_device(shape, dt, seed=seed, std=std, device=dev)
 
 
-def measure(args, wl, ctx):
-    """One workload -> the dict of its bench line (rank 0; other ranks take part in the timed region and return their copy)."""
+def measure(args, wl, ctx, dump_only=False):
+    """One workload -> the dict of its bench line (rank 0; other ranks take part in the timed region and return their copy).
+    dump_only (N = 1): set up, run ONE untimed step, put its output into ctx.dumps and return None."""
     import mps_bitsandbytes_amd as bnb
     from mps_bitsandbytes_amd import _native, synthetic
     from mps_bitsandbytes_amd.sharding import ChunkedGather, row_shard
@@ -596,13 +611,21 @@ def measure(args, wl, ctx):
         flops_per_step = 2.0 * M * N * K
 
     step, finish = modes["main"]
-    # the driver's protocol WITHOUT the time-based pre-warm, measured first (cold clock): W warm-up steps, then K timed steps
-    for _ in range(args.warmup):
-        step()
-    if finish is not None:
-        finish()
-    cold = timer.run(step, finish, args.steps, 1)[0]
-    timer.last = None
+    if dump_only:
+        assert not do_gather
+        last = step()
+        torch.cuda.synchronize()
+        ctx.dumps[wl] = dump_sample(last)
+        return None
+    cold = None
+    if args.full:
+        # the driver's protocol WITHOUT the time-based pre-warm, measured first (cold clock): W warm-up steps, then K timed steps
+        for _ in range(args.warmup):
+            step()
+        if finish is not None:
+            finish()
+        cold = timer.run(step, finish, args.steps, 1)[0]
+        timer.last = None
     prewarm_steps = timer.prewarm(step, finish, args.prewarm_ms) if args.prewarm_ms > 0 else 0
     for _ in range(args.warmup):
         step()
@@ -620,7 +643,7 @@ def measure(args, wl, ctx):
     out["rep_ms_per_step"] = [round(r[0] / args.steps * 1e3, 5) for r in reps]
 
     curves = {}
-    if do_gather:
+    if do_gather and args.full:
         for cname in ("gemm_only", "sync", "overlapped", "chunked"):
             if modes[cname] is modes["main"]:
                 curves[cname] = (elapsed, ev_ms)
@@ -632,9 +655,9 @@ def measure(args, wl, ctx):
                 f_()
             curves[cname] = median_rep(timer.run(s_, f_, args.steps, min(reps_n, 3)))
 
-    # device-side duration of one step: the events of the median repetition (for N > 1: of the gather-free curve)
+    # device-side duration of one step: the events of the median repetition (for N > 1: of the gather-free curve, --full only)
     if do_gather:
-        kern_ms = curves["gemm_only"][1] / args.steps
+        kern_ms = curves["gemm_only"][1] / args.steps if args.full else None
     elif wl == "nf4_m1":
         kern_ms = ev_ms / args.steps / 64
     else:
@@ -655,9 +678,10 @@ def measure(args, wl, ctx):
                                   "int8_4096": "rowwise INT8 matmul_int8 4096x4096x4096 on int8 MFMA (A by row, B [K, N] by column, read in place)",
                                   "nf4_m1": "fused NF4 dequant+GEMV, weight 4096x4096 fp16 bs64, M=1, rotating over 64 layers (one HIP graph of the 64 launches per step)"}[wl],
                      "global_rows": M_global, "rows_per_gpu": M, "N": N, "K": K, "parallelism": par, "kernel": kernel_name}
-    out["no_prewarm"] = {"ms_per_step": round(cold[0] / args.steps * 1e3, 5),
-                         "note": "the same K steps after the W warm-up steps only, BEFORE the time-based pre-warm (cold clock): what a driver-side "
-                                 "timer around a fresh process sees without the disclosed pre-warm"}
+    if cold is not None:
+        out["no_prewarm"] = {"ms_per_step": round(cold[0] / args.steps * 1e3, 5),
+                             "note": "the same K steps after the W warm-up steps only, BEFORE the time-based pre-warm (cold clock): what a driver-side "
+                                     "timer around a fresh process sees without the disclosed pre-warm"}
     traffic = {}
     prof = os.path.join(ROOT, "profiles", "traffic.json")
     if os.path.exists(prof):
@@ -674,21 +698,22 @@ def measure(args, wl, ctx):
         out["metric"] = "effective GB/s, fused NF4 dequant+GEMV 4096x4096 M=1 (HBM, 64 rotating layers)"
         out["value"] = round(bytes_per_launch * 64 * world / (elapsed / args.steps) / 1e9, 2)
         out["unit"] = "GB/s"
-        out["no_prewarm"]["value"] = round(bytes_per_launch * 64 * world / (cold[0] / args.steps) / 1e9, 2)
+        if cold is not None:
+            out["no_prewarm"]["value"] = round(bytes_per_launch * 64 * world / (cold[0] / args.steps) / 1e9, 2)
         out["roofline"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                            "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": traffic.get("k_gemv4_bytes_per_launch"),
                            "kernel_us": round(kern_ms * 1e3, 3), "traffic_source": traffic_source}
     else:
         tflops = total_flops / (elapsed / args.steps) / 1e12
         peak = PEAK_TFLOPS[name]
-        kern_tflops = flops_per_step / (kern_ms * 1e-3) / 1e12
         unit = "TOP/s" if wl == "int8_4096" else "TFLOP/s"
         out["metric"] = {"nf4_m4096": "effective bf16 TFLOPS, NF4 dequant+matmul 4096x4096 @ M=4096 (" + ("dequantise-once + dense GEMM, two launches" if two_launch else "one fused launch") + ")",
                          "nf4dq_ffn": "effective bf16 TFLOPS, NF4 + double-quant matmul 11008x4096 @ M=4096 (" + ("dequantise-once + dense GEMM, two launches" if two_launch else "one fused launch") + ")",
                          "int8_4096": "effective int8 TOPS, rowwise matmul_int8 4096x4096x4096"}[wl]
         out["value"] = round(tflops, 2)
         out["unit"] = unit
-        out["no_prewarm"]["value"] = round(total_flops / (cold[0] / args.steps) / 1e12, 2)
+        if cold is not None:
+            out["no_prewarm"]["value"] = round(total_flops / (cold[0] / args.steps) / 1e12, 2)
         for cname, (el, _) in curves.items():
             out[cname] = {"value": round(total_flops / (el / args.steps) / 1e12, 2), "unit": unit,
                           "ms_per_step": round(el / args.steps * 1e3, 5)}
@@ -699,10 +724,14 @@ def measure(args, wl, ctx):
         # The roofline object describes the OPERATION (the whole step: every launch of it), per GPU: algorithmic flops / step
         # duration by HIP events on the launching stream.  `traffic`: PMC bytes of the step's launches (profiles/traffic.json).
         tkey = {"nf4_m4096": "nf4_m4096_step_bytes", "nf4dq_ffn": "nf4dq_ffn_step_bytes", "int8_4096": "int8_4096_step_bytes"}[wl]
-        out["roofline"] = {"bound": "mfma", "scope": "the whole step (all launches of one matmul call)", "achieved": round(kern_tflops, 2),
-                           "peak": peak, "unit": unit, "frac": round(kern_tflops / peak, 4), "traffic": traffic.get(tkey),
-                           "kernel_us": round(kern_ms * 1e3, 2), "traffic_source": traffic_source,
-                           "kernel_us_note": "HIP events around the K steps of the median repetition / K (includes the inter-launch boundaries)"}
+        if kern_ms is not None:
+            kern_tflops = flops_per_step / (kern_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "scope": "the whole step (all launches of one matmul call)", "achieved": round(kern_tflops, 2),
+                               "peak": peak, "unit": unit, "frac": round(kern_tflops / peak, 4), "traffic": traffic.get(tkey),
+                               "kernel_us": round(kern_ms * 1e3, 2), "traffic_source": traffic_source,
+                               "kernel_us_note": "HIP events around the K steps of the median repetition / K (includes the inter-launch boundaries)"}
+            if two_launch and wl in ("nf4_m4096", "nf4dq_ffn"):
+                out["roofline"]["launches"] = ["k_dequantize_4bit_flat (N x K_weight 16-bit values into the scratch)", "k_gemm_dense"]
         lib, sp = _native.lib(), _native.stream_ptr(dev)
         st_ = torch.cuda.current_stream()
 
@@ -720,7 +749,7 @@ def measure(args, wl, ctx):
                 vals.append(e0.elapsed_time(e1) / args.steps * 1e3)
             return sorted(vals)[len(vals) // 2]
 
-        if two_launch and wl in ("nf4_m4096", "nf4dq_ffn"):
+        if two_launch and wl in ("nf4_m4096", "nf4dq_ffn") and args.full:
             # the step's two launches on their own (same operands, same stream, events around K launches)
             code = _native.DTYPE_CODE[dt]
             Wd = bnb.dequantize_4bit(packed, state)
@@ -737,7 +766,6 @@ def measure(args, wl, ctx):
             dense_us, deq_us = ev_us(dense_only), ev_us(dequant_only)
             assert torch.equal(Yd, bnb.matmul_4bit(X, packed, state)), "dense-only launch differs from the step's output"
             d_tflops = flops_per_step / (dense_us * 1e-6) / 1e12
-            out["roofline"]["launches"] = ["k_dequantize_4bit_flat (N x K_weight 16-bit values into the scratch)", "k_gemm_dense"]
             out["roofline"]["dominant_kernel"] = {
                 "kernel": "k_gemm_dense", "kernel_us": round(dense_us, 2), "achieved": round(d_tflops, 2), "frac": round(d_tflops / peak, 4),
                 "traffic": traffic.get("k_gemm_dense_bytes_per_launch") if wl == "nf4_m4096" else traffic.get("nf4dq_ffn_gemm_dense_bytes_per_launch"),
@@ -782,7 +810,7 @@ def measure(args, wl, ctx):
         out["verified"] = ok
         del full
 
-    if rank == 0 and wl == "nf4_m4096":
+    if rank == 0 and wl == "nf4_m4096" and args.full:
         if not args.no_gemv:
             # the M = 1 half of the metric: HBM-bound decode shape, 64 rotating layers
             layers = []
@@ -904,7 +932,7 @@ def measure(args, wl, ctx):
                     out["roofline"]["ceiling_floor_frac"] = out["roofline"]["ceiling"]["floor_frac"]
             except Exception as e:  # context only: never fails the bench
                 out["roofline"]["empirical"] = {"error": str(e)[:200]}
-    if rank == 0 and wl == "int8_4096" and not args.no_empirical:
+    if rank == 0 and wl == "int8_4096" and args.full and not args.no_empirical:
         # what the int8 matrix pipe sustains on THIS box (bare v_mfma_i32_32x32x32_i8 loop, one wave per SIMD)
         try:
             i8_tops = bare_mfma_rate(1)
@@ -914,7 +942,7 @@ def measure(args, wl, ctx):
                     "bare_mfma_note": "v_mfma_i32_32x32x32_i8 back to back on every SIMD, nothing else: the sustained int8 matrix rate at the clock the chip holds under that load"}
         except Exception as e:  # context only
             out["roofline"]["empirical"] = {"error": str(e)[:200]}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         import oracle
         nproc = oracle.num_threads()
         base = {"nf4_m4096": lambda: cpu_baseline(args, M, N, K, 64, compress, dt), "nf4dq_ffn": lambda: cpu_baseline(args, M, N, K, 64, compress, dt),
@@ -934,8 +962,9 @@ def measure(args, wl, ctx):
 
 
 def digest(out):
-    """All four GPU configs of BASELINE.json in <= 600 characters: [value, roofline frac of the operation, step us, dominant-kernel us]
-    per workload (nf4_m1: [GB/s, frac, us per layer]); batch_sweep_us: M -> us of matmul_4bit at 4096 x 4096."""
+    """The GPU configs of the line (with --full: all four of BASELINE.json) in <= 600 characters: [value, roofline frac of the
+    operation, step us, dominant-kernel us] per workload (nf4_m1: [GB/s, frac, us per layer]); batch_sweep_us: M -> us of
+    matmul_4bit at 4096 x 4096."""
     def row(o):
         r = o.get("roofline") or {}
         return [o.get("value"), r.get("frac"), r.get("kernel_us"), r.get("dom_kernel_us")]
@@ -1006,7 +1035,13 @@ def main():
     ctx.world, ctx.rank, ctx.dev, ctx.dist, ctx.distributed, ctx.rehearse = world, rank, dev, dist, distributed, rehearse
     ctx.dumps = {}
     out = measure(args, wl, ctx)
-    if rank == 0 and world == 1 and wl == "nf4_m4096" and not args.no_secondary:
+    secondary = rank == 0 and world == 1 and wl == "nf4_m4096" and not args.no_secondary
+    if secondary and not args.full and args.dump_outputs:
+        # a plain run times the headline alone, but dumps the secondary workloads' outputs too (one untimed step each)
+        for w2 in ("nf4dq_ffn", "int8_4096", "nf4_m1"):
+            measure(args, w2, ctx, dump_only=True)
+            torch.cuda.empty_cache()
+    if secondary and args.full:
         # the other BASELINE GPU configs under the same clock: configs[2] (11008 x 4096 + double quant), configs[3] (int8 4096^3),
         # configs[1] stand-alone (M = 1 over 64 rotating layers), each with its own roofline / traffic / cpu_baseline
         sec = []

@@ -80,3 +80,37 @@ def test_dump_outputs_hold_the_last_timed_step(tmp_path):
     X = synthetic.normal_device((4096, 4096), torch.bfloat16, seed=4321, std=1.0, device=dev)
     want = bench.dump_sample(bnb.matmul_4bit(X, packed, state))
     assert got.dtype == np.float32 and np.array_equal(got, want)
+
+
+def test_full_flag_is_accepted():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--full"], env=_env(WORLD_SIZE="2", RANK="0"),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--gpus 4 but WORLD_SIZE=2" in p.stdout, p.stderr[-1500:]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_alone_and_dumps_what_full_dumps(tmp_path):
+    """A plain run measures only the headline; --full adds the rest.  Both write the same four arrays, bit for bit (the plain run
+    computes the secondary workloads' outputs with one untimed step each)."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reps", "1", "--prewarm-ms", "0"]
+    recs = {}
+    for form, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-gemv", "--no-empirical"])):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra + ["--dump-outputs", str(tmp_path / form)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        recs[form] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = recs["plain"], recs["full"]
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["kernel_us"] > 0
+    assert not {"secondary", "no_prewarm", "cpu_baseline", "gemv", "batch_sweep"} & set(plain)
+    assert "dominant_kernel" not in plain["roofline"] and "empirical" not in plain["roofline"]
+    assert [o["workload_key"] for o in full["secondary"]] == ["nf4dq_ffn", "int8_4096", "nf4_m1"]
+    assert not [o["error"] for o in full["secondary"] if "error" in o]
+    assert "no_prewarm" in full and "dominant_kernel" in full["roofline"]
+    names = ["nf4_m4096", "nf4dq_ffn", "int8_4096", "nf4_m1"]
+    assert list(plain["dumped_outputs"]) == names and plain["dumped_outputs"] == full["dumped_outputs"]
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n

@@ -1031,7 +1031,7 @@ def test_bench_gpus_flag_spawns_ranks_and_gathers_the_unsharded_result():
     env["BENCH_REHEARSE"] = "1"
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--reps", "2", "--prewarm-ms", "0", "--no-cpu-baseline", "--no-gemv", "--no-empirical", "--verify"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -1058,7 +1058,7 @@ def test_bench_two_ranks_on_the_real_nccl_backend():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
                         "--reps", "2", "--prewarm-ms", "0", "--no-cpu-baseline", "--no-gemv", "--no-empirical", "--verify"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]

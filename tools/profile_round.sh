@@ -8,17 +8,17 @@ tag=${1:-r02}
 export TMPDIR=/tmp
 o=gpurun_out
 mkdir -p $o
-# the driver's form of the bench line (steps 20, warm-up 5) and the default form
-python3 bench.py --steps 20 --warmup 5 > $o/${tag}_bench_driver.json 2> $o/${tag}_bench_driver.err
-python3 bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+# the driver's form of the bench line (steps 20, warm-up 5) and the default form, each with everything --full measures
+python3 bench.py --full --steps 20 --warmup 5 > $o/${tag}_bench_driver.json 2> $o/${tag}_bench_driver.err
+python3 bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-empirical --no-secondary > $o/${tag}_trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_trace -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-empirical --no-secondary > $o/${tag}_trace.log 2>&1
 echo "trace done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_nf4dq_ffn -- python3 bench.py --workload nf4dq_ffn --no-cpu-baseline --steps 50 > $o/${tag}_nf4dq_ffn.json 2> $o/${tag}_nf4dq_ffn.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_int8_4096 -- python3 bench.py --workload int8_4096 --no-cpu-baseline --steps 50 > $o/${tag}_int8_4096.json 2> $o/${tag}_int8_4096.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_nf4_m1 -- python3 bench.py --workload nf4_m1 --no-cpu-baseline --steps 20 > $o/${tag}_nf4_m1.json 2> $o/${tag}_nf4_m1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_nf4dq_ffn -- python3 bench.py --full --workload nf4dq_ffn --no-cpu-baseline --steps 50 > $o/${tag}_nf4dq_ffn.json 2> $o/${tag}_nf4dq_ffn.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_int8_4096 -- python3 bench.py --full --workload int8_4096 --no-cpu-baseline --steps 50 > $o/${tag}_int8_4096.json 2> $o/${tag}_int8_4096.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_nf4_m1 -- python3 bench.py --full --workload nf4_m1 --no-cpu-baseline --steps 20 > $o/${tag}_nf4_m1.json 2> $o/${tag}_nf4_m1.err
 echo "workload traces done"
-small="--no-cpu-baseline --no-gemv --no-empirical --no-secondary --steps 5 --warmup 3 --reps 2 --prewarm-ms 50"
+small="--full --no-cpu-baseline --no-gemv --no-empirical --no-secondary --steps 5 --warmup 3 --reps 2 --prewarm-ms 50"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $o/${tag}_fetch -- python3 bench.py $small > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $o/${tag}_write -- python3 bench.py $small > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $o/${tag}_tcc -- python3 bench.py $small > /dev/null 2>&1
