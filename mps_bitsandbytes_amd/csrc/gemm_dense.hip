@@ -168,6 +168,7 @@ static int launch_gemm_dense_fm(const T *x, const T *wd, const T *bias, void *ou
         hipLaunchKernelGGL((k_splitk_reduce_rm<T, f16_t>), dim3(blocks), dim3(256), 0, st, partial, (int)used, bias, static_cast<f16_t *>(out), M, N);
     else
         hipLaunchKernelGGL((k_splitk_reduce_rm<T, bf16_t>), dim3(blocks), dim3(256), 0, st, partial, (int)used, bias, static_cast<bf16_t *>(out), M, N);
+    set_kernel_name(FM == 8 ? "dense 256x256_splitk" : "dense 256x128_splitk");
     return check_launch("matmul_4bit(dense split-K reduce)");
 }
 
@@ -203,6 +204,7 @@ static int launch_gemm_dense128(const T *x, const T *wd, const T *bias, void *ou
     auto kern = k_gemm_dense128<T>;
     if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), G128_LDS, "matmul_4bit(dense128)")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), G128_LDS, st, x, wd, bias, out, out_dtype, M, N, K, ldw);
+    set_kernel_name("dense 128x128");
     return check_launch("matmul_4bit(dense128)");
 }
 

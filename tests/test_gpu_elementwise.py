@@ -1,0 +1,335 @@
+"""
+Every kernel the library can report, element by element against float64, on poisoned allocations.
+
+The cases are the table of tests/kernel_cases.py.  Each runs through the public API (mbnb_gemm_dense through the C ABI) right
+after a one-row embedding lookup whose kernel name is known, so a launch that sets no name shows up as that name instead of
+passing on a stale one; it must dispatch to its named kernel, and every output element must lie within the bound of
+tests/elementwise.py around a float64 product of the operands the op feeds the kernel -- the decoded weight taken from the CPU
+oracle, and the library's own dequantise checked against it bit for bit.  Outputs and workspaces come from functional.py's
+poisoned torch.empty (tests/poison.py), or are poisoned by hand where a test allocates them.  The largest err / bound ratio
+of every case is printed (run with -s).
+"""
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from mps_bitsandbytes_amd import _native, synthetic
+from mps_bitsandbytes_amd import functional as F
+from tests import kernel_cases
+from tests.elementwise import (UNIT, assert_bound_elementwise, assert_int8_elementwise, assert_linear_elementwise,
+                               int8_reference)
+from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_alloc")]
+
+DEV = "cuda"
+DT = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
+_SENTINEL = {}
+
+
+def _poison(t):
+    t.reshape(-1).view(torch.uint8).fill_(0xFF)
+    return t
+
+
+def _sentinel(kernel):
+    """Run a one-row embedding lookup (not the case's own kernel) and return its name."""
+    if not _SENTINEL:
+        _SENTINEL["q8"] = torch.ones(4, 64, dtype=torch.int8, device=DEV)
+        _SENTINEL["s8"] = torch.ones(4, dtype=torch.float32, device=DEV)
+        _SENTINEL["p4"] = torch.zeros(4, 32, dtype=torch.uint8, device=DEV)
+        _SENTINEL["a4"] = torch.ones(4, 1, dtype=torch.float32, device=DEV)
+    idx = torch.zeros(1, dtype=torch.int64, device=DEV)
+    if kernel == "embedding8":
+        F.embedding_4bit(idx, _SENTINEL["p4"], _SENTINEL["a4"], 64)
+        name = "embedding4"
+    else:
+        F.embedding_8bit(idx, _SENTINEL["q8"], _SENTINEL["s8"])
+        name = "embedding8"
+    assert _native.last_kernel() == name
+    return name
+
+
+def _check_name(got, c):
+    want = c["kernel"]
+    ok = got.startswith(want) if want.endswith(" ") else got == want
+    assert ok, f"{kernel_cases.case_id(c)}: dispatched {got!r}, the case is for {want!r}"
+
+
+def _same_bits(a, b):
+    """Bit-equal wherever a value is a number, NaN in the same places (NaN payloads and signs may differ)."""
+    a, b = a.detach().cpu(), b.detach().cpu()
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    nan = torch.isnan(a)
+    if not torch.equal(nan, torch.isnan(b)):
+        return False
+    iv = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    return torch.equal(torch.where(nan, 0, a).view(iv), torch.where(nan, 0, b).view(iv))
+
+
+def _activation(c, K, dt, seed):
+    """X as the op is fed it: rows scaled by 2^e, non-finite values planted, a row slice or a misaligned view if asked."""
+    lead = tuple(c["lead"]) if "lead" in c else (c["M"],)
+    rows = int(np.prod(lead))
+    X = synthetic.normal_device((rows, K), dt, seed=seed)
+    if "xexp" in c:
+        lo, hi = c["xexp"]
+        e = torch.linspace(lo, hi, rows, device=DEV).round().double()
+        X = (X.double() * torch.exp2(e)[:, None]).to(dt)
+    if "x" in c.get("bad", ""):
+        X[1 % rows, 3] = float("nan")
+        X[3 % rows, 5] = float("inf")
+        X[4 % rows, 9] = float("-inf")
+    if c.get("view") == "rows":
+        big = synthetic.normal_device((rows + 4, K), dt, seed=seed + 1)
+        big[3:3 + rows] = X
+        X = big[3:3 + rows]
+    elif c.get("view") == "misaligned":
+        flat = torch.empty(rows * K + 1, dtype=dt, device=DEV)
+        flat[1:] = X.reshape(-1)
+        X = flat[1:].view(rows, K)
+        assert X.data_ptr() % 16 == 2
+    return X.reshape(*lead, K)
+
+
+def _bias(c, N, dt, seed):
+    return synthetic.normal_device((N,), dt, seed=seed) if c.get("bias") else None
+
+
+def _weight_4bit(c, N, K, dt, seed):
+    """(packed, QuantState) on the GPU and the oracle's decoded weight [N, K] (a NaN absmax in one block for bad "w")."""
+    qt, bs, cs = c.get("qt", "nf4"), c.get("bs", 64), c.get("cs", False)
+    W = synthetic.normal((N, K), dt, seed=seed)
+    op, oa, ost2 = oracle.quantize_4bit(W, bs, qt, cs)
+    if "w" in c.get("bad", ""):
+        assert not cs
+        oa = oa.clone()
+        oa[oa.numel() // 3] = float("nan")
+    Wd = oracle.dequantize_4bit(op, oa, (N, K), bs, qt, dt, ost2)
+    st2 = None
+    if cs:
+        st2 = F.QuantState(absmax=ost2[0].to(DEV), shape=torch.Size([oa.numel()]), blocksize=ost2[1], quant_type="int8", dtype=torch.float32)
+    st = F.QuantState(absmax=oa.to(DEV), shape=torch.Size([N, K]), blocksize=bs, quant_type=qt, dtype=dt, state2=st2)
+    packed = op.to(DEV)
+    assert _same_bits(F.dequantize_4bit(packed, st), Wd), "dequantize_4bit differs from the oracle's decode"
+    return packed, st, Wd
+
+
+def _weight_8bit(c, N, K, dt, seed, fp8):
+    """(q, scales) on the GPU and the oracle's decoded weight (a NaN row scale / FP8 byte 0x7F for bad "w")."""
+    W = synthetic.normal((N, K), dt, seed=seed, std=0.05)
+    q, s = (oracle.quantize_fp8_e4m3 if fp8 else oracle.quantize_rowwise)(W)
+    if "w" in c.get("bad", ""):
+        if fp8:
+            q = q.clone()
+            q[N // 2, K // 3] = 0x7F
+        else:
+            s = s.clone()
+            s[N // 2] = float("nan")
+    Wd = (oracle.dequantize_fp8_e4m3 if fp8 else oracle.dequantize_rowwise)(q, s, dt)
+    qd, sd = q.to(DEV), s.to(DEV)
+    mine = (F.dequantize_fp8_e4m3 if fp8 else F.dequantize_rowwise)(qd, sd, dt)
+    assert _same_bits(mine, Wd), "the library's dequantise differs from the oracle's"
+    return qd, sd, Wd
+
+
+def _run_linear(c, monkeypatch):
+    op, N, K, dt = c["op"], c["N"], c["K"], DT[c["dt"]]
+    if c.get("fused"):
+        monkeypatch.setattr(F, "DECODE_ONCE", False)
+    X = _activation(c, K, dt, seed=11)
+    b = _bias(c, N, dt, seed=12)
+    out = DT.get(c.get("out"))
+    if op == "matmul_4bit":
+        packed, st, Wd = _weight_4bit(c, N, K, dt, seed=13)
+        _sentinel(c["kernel"])
+        y = F.matmul_4bit(X, packed, st, b, out)
+    elif op in ("linear_int8", "matmul_fp8"):
+        q, s, Wd = _weight_8bit(c, N, K, dt, seed=13, fp8=op == "matmul_fp8")
+        _sentinel(c["kernel"])
+        y = F.linear_int8(X, q, s, b) if op == "linear_int8" else F.matmul_fp8_e4m3(X, q, s, b, dt)
+    else:
+        Wd = synthetic.normal_device((N, K), dt, seed=13, std=0.05)
+        _sentinel(c["kernel"])
+        y = F.linear_dense(X, Wd, b)
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    return kern, assert_linear_elementwise(y, X, Wd, b, dt, out or dt, kern)
+
+
+def _run_gemm_dense(c):
+    M, N, K, ldw, dt = c["M"], c["N"], c["K"], c["ldw"], DT[c["dt"]]
+    odt = DT[c.get("out", c["dt"])]
+    lib = _native.lib()
+    X = _activation(c, K, dt, seed=21)
+    Wfull = synthetic.normal_device((N, ldw), dt, seed=22, std=0.05)
+    b = _bias(c, N, dt, seed=23)
+    out = _poison(torch.empty(M, N, dtype=odt, device=DEV))
+    slices = c["slices"]
+    ws = _poison(torch.empty(slices * M * N * 4, dtype=torch.uint8, device=DEV)) if slices > 1 else None
+    code = _native.DTYPE_CODE[dt]
+    _sentinel(c["kernel"])
+    rc = lib.mbnb_gemm_dense(X.data_ptr(), Wfull.data_ptr(), code, None if b is None else b.data_ptr(), _native.DTYPE_CODE[odt],
+                             out.data_ptr(), M, N, K, ldw, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
+                             slices | (c["tile"] << 8), _native.stream_ptr(DEV))
+    assert rc == 0, lib.mbnb_last_error()
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    return kern, assert_linear_elementwise(out, X, Wfull[:, :K], b, dt, odt, kern)
+
+
+def _run_matmul_int8(c):
+    M, N, K = c["M"], c["N"], c["K"]
+    odt = DT[c["out"]]
+    A = synthetic.int8_tensor((M, K), seed=31).to(DEV)
+    B = synthetic.int8_tensor((K, N), seed=32).to(DEV)
+    sa = (synthetic.normal((M,), torch.float32, seed=33).abs() + 0.5).to(DEV)
+    sb = (synthetic.normal((N,), torch.float32, seed=34).abs() + 0.5).to(DEV)
+    if "w" in c.get("bad", ""):
+        sb[N // 2] = float("nan")
+    _sentinel(c["kernel"])
+    y = F.matmul_int8(A, B, sa, sb, odt)
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    return kern, assert_int8_elementwise(y, int8_reference(A, B, sa, sb), odt, kern)
+
+
+def _run_grad(c):
+    """dX = cast(round_w(dY.to(w_dtype) . dequant(W)), x.dtype): the contraction runs over N."""
+    M, N, K, dt, fmt = c["M"], c["N"], c["K"], DT[c["dt"]], c["fmt"]
+    if fmt == "4bit":
+        packed, st, Wd = _weight_4bit(c, N, K, dt, seed=41)
+        fwd = lambda x: F.matmul_4bit(x, packed, st)            # noqa: E731
+    else:
+        q, s, Wd = _weight_8bit(c, N, K, dt, seed=41, fp8=fmt == "fp8")
+        fwd = (lambda x: F.linear_int8(x, q, s)) if fmt == "int8" else (lambda x: F.matmul_fp8_e4m3(x, q, s, None, dt))  # noqa: E731
+    x = synthetic.normal_device((M, K), dt, seed=42).requires_grad_(True)
+    dY = _activation(dict(c, M=M), N, dt, seed=43)
+    seen = []
+    y = fwd(x)
+    # both hooks run on autograd's device thread, whose last-kernel record is its own: the sentinel just before the backward
+    # of the op, the name just after it
+    y.register_hook(lambda g: seen.append(_sentinel(c["kernel"])) and None)
+    x.register_hook(lambda g: seen.append(_native.last_kernel()) and None)
+    y.backward(dY)
+    assert len(seen) == 2, seen
+    kern = seen[1]
+    _check_name(kern, c)
+    return kern, assert_linear_elementwise(x.grad, dY, Wd.t().contiguous().to(DEV), None, dt, dt, kern)
+
+
+def _run_grad_t(c):
+    """The transposed dequantise pass alone: bit for bit the oracle's decode, transposed."""
+    N, K, dt, fmt = c["N"], c["K"], DT[c["dt"]], c["fmt"]
+    if fmt == "4bit":
+        packed, st, Wd = _weight_4bit(c, N, K, dt, seed=51)
+        _sentinel(c["kernel"])
+        Wt = F._dequantize_t(packed, st)
+    else:
+        q, s, Wd = _weight_8bit(c, N, K, dt, seed=51, fp8=fmt == "fp8")
+        _sentinel(c["kernel"])
+        Wt = F._dequantize_t(q, scales=s, fmt=fmt, dtype=dt)
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    assert _same_bits(Wt, Wd.t().contiguous()), f"{kern}: the transposed pass differs from the oracle's decode"
+    return kern, 0.0
+
+
+def _run_outlier(c):
+    """OutlierAwareLinear against oracle.outlier_linear on every element.  Both quantise the non-outlier columns of x row-wise
+    to int8 the same way; the kernel contracts the integers exactly where the oracle multiplies the decoded operands rounded to
+    the compute dtype (the reference's numerics), so the bound is 2 ulps of |ref| (the two final roundings), 3 u + g over the
+    decomposition S = (|x| + max|x_row| / 127) . |Wd|^T + |b| (the two operand roundings and the accumulation), and one int8 step
+    of x on one element of the row (a tie quantised the other way)."""
+    M, N, K, dt, n_out = c["M"], c["N"], c["K"], DT[c["dt"]], c["n_out"]
+    W = synthetic.normal((N, K), torch.float32, seed=61, std=0.05)
+    oidx = torch.from_numpy(np.sort((synthetic.uniform_u64(4 * n_out + 1, seed=62) % np.uint64(K)).astype(np.int64))).unique()[:n_out]
+    W[:, oidx] *= 30.0
+    W = W.to(dt)
+    W0 = W.clone()
+    W0[:, oidx] = 0
+    q, s = oracle.quantize_rowwise(W0)
+    ow = W[:, oidx].contiguous()
+    b = synthetic.normal((N,), dt, seed=63) if c.get("bias") else None
+    x = synthetic.normal((M, K), dt, seed=64)
+    _sentinel(c["kernel"])
+    y = F.outlier_linear(x.to(DEV), q.to(DEV), s.to(DEV), oidx.to(DEV), ow.to(DEV), None if b is None else b.to(DEV), dt)
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    ref = oracle.outlier_linear(x, q, s, oidx, ow, b).to(DEV).double()
+    Wfull = oracle.dequantize_rowwise(q, s, dt).to(DEV).double()
+    Wfull[:, oidx.to(DEV)] = ow.to(DEV).double()
+    xd = x.to(DEV).double()
+    step = xd.abs().amax(1, keepdim=True) / 127.0
+    S = (xd.abs() + step) @ Wfull.abs().t() + (0 if b is None else b.to(DEV).double().abs())
+    u = UNIT[dt]
+    g = (K + 2) * 2.0 ** -23
+    bound = 4 * u * ref.abs() + (3 * u + g) * S + step * Wfull.abs().amax(1)[None, :] + (2.0 ** -24 if dt == torch.float16 else 0.0)
+    return kern, assert_bound_elementwise(y, ref, bound, kern, "outlier_linear")
+
+
+def _run_embedding(c):
+    M, dim, num, dt = c["M"], c["N"], c["K"], DT[c["dt"]]
+    idx = torch.from_numpy((synthetic.uniform_u64(M, seed=71) % np.uint64(num)).astype(np.int64))
+    if c["op"] == "embedding_4bit":
+        W = synthetic.normal((num, dim), dt, seed=72)
+        op, oa, _ = oracle.quantize_4bit(W, c["bs"], c["qt"])
+        packed, absmax = op.view(num, dim // 2), oa.view(num, -1)
+        ref = oracle.embedding_4bit(idx, packed, absmax, dim, c["bs"], c["qt"], None, dt)
+        _sentinel(c["kernel"])
+        y = F.embedding_4bit(idx.to(DEV), packed.to(DEV), absmax.to(DEV), dim, c["bs"], c["qt"], None, dt)
+    else:
+        W = synthetic.normal((num, dim), dt, seed=72)
+        q, s = oracle.quantize_rowwise(W)
+        ref = oracle.embedding_8bit(idx, q, s, None, dt)
+        _sentinel(c["kernel"])
+        y = F.embedding_8bit(idx.to(DEV), q.to(DEV), s.to(DEV), None, dt)
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    assert _same_bits(y, ref), f"{kern} differs from the oracle"
+    return kern, 0.0
+
+
+@pytest.mark.parametrize("case", [pytest.param(c, marks=pytest.mark.xfail(strict=True, reason=c["xfail"])) if "xfail" in c else c
+                                  for c in kernel_cases.CASES], ids=[kernel_cases.case_id(c) for c in kernel_cases.CASES])
+def test_kernel_case_elementwise(case, monkeypatch, poisoned_alloc):
+    op = case["op"]
+    if op in ("matmul_4bit", "linear_int8", "matmul_fp8", "linear_dense"):
+        kern, ratio = _run_linear(case, monkeypatch)
+    elif op == "gemm_dense":
+        kern, ratio = _run_gemm_dense(case)
+    elif op == "matmul_int8":
+        kern, ratio = _run_matmul_int8(case)
+    elif op == "grad":
+        kern, ratio = _run_grad(case)
+    elif op == "grad_t":
+        kern, ratio = _run_grad_t(case)
+    elif op == "outlier_linear":
+        kern, ratio = _run_outlier(case)
+    else:
+        kern, ratio = _run_embedding(case)
+    assert poisoned_alloc.poisoned > 0
+    print(f"\nelementwise {kern}: max err / bound {ratio:.3g} ({kernel_cases.case_id(case)})")
+
+
+def test_matmul_int8_transpose_path_at_the_offset_limit(poisoned_alloc):
+    """K * N = 2^31 (M = 256, N = 65536, K = 32768): past the in-place kernel's 32-bit offsets (gemm_i8_inplace.hip), B -- a
+    2 GiB int8 matrix -- is transposed into the workspace and multiplied by the dense pipeline.  Every element against the exact
+    integer product, computed in column chunks (no float64 copy of B)."""
+    M, N, K = 256, 65536, 32768
+    g = torch.Generator(device=DEV).manual_seed(20261016)
+    A = torch.randint(-127, 128, (M, K), generator=g, device=DEV, dtype=torch.int8)
+    B = torch.randint(-127, 128, (K, N), generator=g, device=DEV, dtype=torch.int8)
+    sa = torch.rand(M, generator=g, device=DEV) + 0.5
+    sb = torch.rand(N, generator=g, device=DEV) + 0.5
+    _sentinel("i8_transpose+dense")
+    y = F.matmul_int8(A, B, sa, sb, torch.bfloat16)
+    kern = _native.last_kernel()
+    assert kern == "i8_transpose+dense", kern
+    ref = int8_reference(A, B, sa, sb, chunk=4096)
+    del B
+    ratio = assert_int8_elementwise(y, ref, torch.bfloat16, kern)
+    assert poisoned_alloc.poisoned > 0
+    print(f"\nelementwise {kern}: max err / bound {ratio:.3g} (M={M} N={N} K={K})")

@@ -13,8 +13,9 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _native, synthetic
 from mps_bitsandbytes_amd import functional as F
 from tests.goldenio import DT, from_bits, rel_fro
+from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name: every torch.empty of functional.py comes back 0xFF)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_alloc")]
 
 DEV = "cuda"
 TOL = {torch.float16: 2e-4, torch.bfloat16: 2e-3, torch.float32: 2e-6}     # the gates of test_gpu_parity.py

@@ -16,8 +16,9 @@ import oracle
 import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _native, synthetic
 from tests.goldenio import DT, HERE, bits_equal, from_bits, n_mismatch, rel_fro
+from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name: every torch.empty of functional.py comes back 0xFF)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_alloc")]
 DEV = "cuda"
 OA_TOL = {torch.float16: 1e-3, torch.bfloat16: 4e-3}
 

@@ -15,8 +15,9 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _native, synthetic
 from mps_bitsandbytes_amd.functional import QuantState
 from tests.goldenio import DT, bits_equal, from_bits, n_mismatch, rel_fro
+from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name: every torch.empty of functional.py comes back 0xFF)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_alloc")]
 
 DEV = "cuda"
 
