@@ -20,7 +20,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _native
+from . import _native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -964,6 +964,144 @@ def _dequantize_t(weight: Tensor, quant_state: Optional[QuantState] = None, scal
             None, 0, N, code, ptr(W), None if desc is None else ctypes.byref(desc), ptr(s), K, K_weight, int(blocksize), w_code, w_code,
             ptr(out), None, 0, _native.GRAD_TRANSPOSE_ONLY, stream_ptr(W.device)), "_dequantize_t")
     return out
+
+
+# ============================================================================= SwitchBack (trainable int8 linear)
+# SwitchBackLinear (reference nn/switchback.py) keeps an int8 copy of its weight for the forward and a 16-bit master weight `weight_fp`
+# that receives the gradient.  The forward restates SwitchBackFunction.forward: Wd = round_T(q * round_T(s / 127)) -- not
+# dequantize_rowwise, which rounds once -- then round_T(X . Wd^T), then `+ bias` as a separate op (libmbnb_train.so,
+# include/mbnb_train.h).  The backward is the reference's three products on weight_fp: dX = dY . weight_fp through
+# mbnb_linear_grad_input's dense format, dW = dY^T . X through mbnb_linear_grad_weight, db = dY summed over rows in f32.
+def _switchback_forward(input: Tensor, weight_int8: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None, flags: int = 0) -> Tensor:
+    """``input[..., K] . Wd^T (+ bias)`` with SwitchBack's weight rule, in the input's dtype.  A bias of another dtype is added the way the
+    reference adds it (torch's `output + bias`, with type promotion).  `flags`: include/mbnb_train.h, for tests."""
+    _check_device(input, "switchback_linear")
+    _check_device(weight_int8, "switchback_linear")
+    dtype = input.dtype
+    dcode = dtype_code(dtype, "switchback_linear")
+    N, K = weight_int8.shape
+    if input.shape[-1] != K:
+        raise RuntimeError(f"switchback_linear: input width {input.shape[-1]} does not match weight {tuple(weight_int8.shape)}")
+    x = _as(input.reshape(-1, K), dtype)
+    M = x.shape[0]
+    w = _as(weight_int8, torch.int8)
+    s = _as(weight_scales, torch.float32, x.device)
+    if s.numel() != N:
+        raise ValueError(f"weight_scales has {s.numel()} elements, expected {N}")
+    b = late = None
+    if bias is not None:
+        if bias.dtype == dtype:
+            b = _as(bias, dtype, x.device)
+        else:
+            late = bias
+    out = torch.empty(M, N, dtype=dtype, device=x.device)
+    handle = _train_native.lib()
+    ws_bytes = int(handle.mbnb_switchback_forward_workspace_bytes(M, N, K, dcode))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None
+    with on_device(x.device):
+        _train_native.check(handle.mbnb_switchback_forward(ptr(x), dcode, M, K, ptr(w), ptr(s), N, ptr(b), ptr(out), ptr(ws), ws_bytes,
+                                                           int(flags), stream_ptr(x.device)), "switchback_linear")
+    if late is not None:
+        out = out + late.to(x.device)
+    return out.reshape(*input.shape[:-1], N)
+
+
+def _switchback_dequant(weight_int8: Tensor, weight_scales: Tensor, dtype: torch.dtype) -> Tensor:
+    """The forward's first pass on its own: Wd [N, K] = round_T(q * round_T(s / 127)) in `dtype`, the bits its GEMM reads.  For tests
+    and tools."""
+    _check_device(weight_int8, "_switchback_dequant")
+    w = _as(weight_int8, torch.int8)
+    N, K = w.shape
+    s = _as(weight_scales, torch.float32, w.device)
+    dcode = dtype_code(dtype, "_switchback_dequant")
+    out = torch.empty(N, K, dtype=dtype, device=w.device)
+    with on_device(w.device):
+        _train_native.check(_train_native.lib().mbnb_switchback_forward(None, dcode, 0, K, ptr(w), ptr(s), N, None, ptr(out), None, 0,
+                                                                        _train_native.PASS_ONLY, stream_ptr(w.device)), "_switchback_dequant")
+    return out
+
+
+def _linear_grad_weight(grad_output: Tensor, input: Tensor, flags: int = 0) -> Tensor:
+    _check_device(grad_output, "linear_grad_weight")
+    _check_device(input, "linear_grad_weight")
+    dtype = grad_output.dtype
+    if input.dtype != dtype:
+        raise RuntimeError(f"linear_grad_weight: expected grad_output and input to have the same dtype, but got: {dtype} != {input.dtype}")
+    dcode = dtype_code(dtype, "linear_grad_weight")
+    N, K = grad_output.shape[-1], input.shape[-1]
+    g = _as(grad_output.reshape(-1, N), dtype)
+    x = _as(input.reshape(-1, K), dtype, g.device)
+    M = g.shape[0]
+    if x.shape[0] != M:
+        raise RuntimeError(f"linear_grad_weight: grad_output has {M} rows, input {x.shape[0]}")
+    dW = torch.empty(N, K, dtype=dtype, device=g.device)
+    handle = _train_native.lib()
+    ws_bytes = int(handle.mbnb_linear_grad_weight_workspace_bytes(M, N, K, dcode))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes > 0 else None
+    with on_device(g.device):
+        _train_native.check(handle.mbnb_linear_grad_weight(ptr(g), ptr(x), M, N, K, dcode, ptr(dW), ptr(ws), ws_bytes, int(flags),
+                                                           stream_ptr(g.device)), "linear_grad_weight")
+    return dW
+
+
+def linear_grad_weight(grad_output: Tensor, input: Tensor) -> Tensor:
+    """The weight gradient of a linear: ``dW[N, K] = grad_output[..., N]^T . input[..., K]``, summed over every leading position, in the
+    common dtype (f16 / bf16 / f32), f32 accumulation, one rounding -- torch.mm(grad_output_2d.t(), input_2d) of the reference's
+    SwitchBackFunction.backward."""
+    return _linear_grad_weight(grad_output, input)
+
+
+def _transpose_pad(input: Tensor) -> Tensor:
+    """The weight gradient's transposing pass on its own: a 16-bit [M, C] matrix as [C, Mp] with zero columns M .. Mp-1 (Mp: M rounded up
+    to a multiple of 64, at least 128), the operand layout its GEMM reads.  For tests and tools."""
+    _check_device(input, "_transpose_pad")
+    x = input.contiguous()
+    M, C = x.shape
+    dcode = dtype_code(x.dtype, "_transpose_pad")
+    out = torch.empty(C, _train_native.padded_rows(M), dtype=x.dtype, device=x.device)
+    with on_device(x.device):
+        _train_native.check(_train_native.lib().mbnb_linear_grad_weight(None, ptr(x), M, 0, C, dcode, ptr(out), None, 0, _train_native.PASS_ONLY,
+                                                                        stream_ptr(x.device)), "_transpose_pad")
+    return out
+
+
+def _same_dtype(a: Tensor, b: Tensor) -> None:
+    """torch.mm's check, where the reference's backward multiplies two tensors of different dtypes."""
+    if a.dtype != b.dtype:
+        raise RuntimeError(f"SwitchBackLinear backward: expected mat1 and mat2 to have the same dtype, but got: {a.dtype} != {b.dtype}")
+
+
+class _SwitchBackFunction(torch.autograd.Function):
+    """SwitchBackFunction of the reference: int8 forward, backward on the 16-bit master weight."""
+
+    @staticmethod
+    def forward(ctx, input, weight_int8, weight_scales, weight_fp, bias):
+        ctx.save_for_backward(input, weight_fp, bias)
+        return _switchback_forward(input, weight_int8, weight_scales, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        input, weight_fp, bias = ctx.saved_tensors
+        N, K = weight_fp.shape
+        g = grad_output.reshape(-1, grad_output.shape[-1])
+        dX = dW = db = None
+        if ctx.needs_input_grad[0]:
+            _same_dtype(g, weight_fp)
+            w = weight_fp if weight_fp.is_contiguous() else weight_fp.contiguous()
+            dX = _grad_input(_as(g, w.dtype), _FMT_DENSE, w, None, None, K, K, 0, w.dtype, w.dtype).reshape(input.shape)
+        if ctx.needs_input_grad[3]:
+            _same_dtype(g, input)
+            dW = _linear_grad_weight(g, input.reshape(-1, K))
+        if bias is not None and ctx.needs_input_grad[4]:
+            db = g.sum(0, dtype=torch.float32).to(g.dtype)
+        return dX, None, None, dW, db
+
+
+def switchback_linear(input: Tensor, weight_int8: Tensor, weight_scales: Tensor, weight_fp: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """SwitchBackLinear's product (reference SwitchBackFunction.apply): the forward on the int8 weight, the gradients on `weight_fp`.
+    The same kernels run with or without grad mode, so the output bits do not depend on it."""
+    return _SwitchBackFunction.apply(input, weight_int8, weight_scales, weight_fp, bias)
 
 
 # ============================================================================= quantized embedding lookups
