@@ -21,6 +21,8 @@ from .functional import (
     double_quant, dequant_absmax, embedding_4bit, embedding_8bit, outlier_linear,
     quantize_fp8_e4m3, dequantize_fp8_e4m3, matmul_fp8_e4m3,
     switchback_linear, linear_grad_weight,
+    quantize_colrow, dequantize_colrow, matmul_colrow,
+    sparse_coo_from_dense, quantize_sparse_coo, spmm_coo, spmm_coo_int8,
 )
 from .nn import (Linear4bit, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
                  OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback)
@@ -53,5 +55,7 @@ __all__ = [
     'OutlierAwareLinear', 'embedding_4bit', 'embedding_8bit', 'outlier_linear',
     'LinearFP8', 'quantize_fp8_e4m3', 'dequantize_fp8_e4m3', 'matmul_fp8_e4m3',
     'SwitchBackLinear', 'SwitchBackLinearCallback', 'switchback_linear', 'linear_grad_weight',
+    'quantize_colrow', 'dequantize_colrow', 'matmul_colrow',
+    'sparse_coo_from_dense', 'quantize_sparse_coo', 'spmm_coo', 'spmm_coo_int8',
     'BitsAndBytesConfig', 'quantize_model', 'replace_linear_with_4bit', 'replace_linear_with_8bit', 'get_memory_footprint',
 ]

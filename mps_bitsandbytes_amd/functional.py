@@ -20,7 +20,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _native, _train_native
+from . import _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -1102,6 +1102,253 @@ def switchback_linear(input: Tensor, weight_int8: Tensor, weight_scales: Tensor,
     """SwitchBackLinear's product (reference SwitchBackFunction.apply): the forward on the int8 weight, the gradients on `weight_fp`.
     The same kernels run with or without grad mode, so the output bits do not depend on it."""
     return _SwitchBackFunction.apply(input, weight_int8, weight_scales, weight_fp, bias)
+
+
+# ============================================================================= INT8 with column + row statistics (LLM.int8 style)
+# reference functional.py:896-945, on libmbnb_sparse.so (include/mbnb_sparse.h).  The scale of element [i, j] is sqrt(row_absmax[i] *
+# col_absmax[j]); every step of the reference's f32 chain is restated with correctly rounded operations (DESIGN.md section 12).
+def _f32_vector(t: Tensor, n: int, name: str, device) -> Tensor:
+    v = _as(t, torch.float32, device).reshape(-1)
+    if v.numel() != n:
+        raise ValueError(f"{name} has {v.numel()} elements, expected {n}")
+    return v
+
+
+def quantize_colrow(tensor: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """
+    Quantize a matrix to INT8 with both row-wise and column-wise statistics (reference: functional.py:896-924): the scale of
+    element [i, j] is the geometric mean ``sqrt(row_absmax[i] * col_absmax[j])``.
+
+    Returns (int8 [rows, cols], row_absmax f32 [rows], col_absmax f32 [cols]).  Bit-exact with the reference's chain evaluated with
+    a correctly rounded sqrt; a NaN or Inf element makes its row's and column's statistic NaN / Inf and their codes 0.
+    """
+    if tensor.dim() != 2:
+        raise ValueError("Input must be 2D")
+    _check_device(tensor, "quantize_colrow")
+    t = tensor if tensor.is_contiguous() else tensor.contiguous()
+    R, C = t.shape
+    dcode = dtype_code(t.dtype, "quantize_colrow")
+    q = torch.empty((R, C), dtype=torch.int8, device=t.device)
+    rs = torch.empty(R, dtype=torch.float32, device=t.device)
+    cs = torch.empty(C, dtype=torch.float32, device=t.device)
+    handle = _sparse_native.lib()
+    ws_bytes = int(handle.mbnb_colrow_quantize_workspace_bytes(R, C))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device) if ws_bytes > 0 else None
+    with on_device(t.device):
+        _sparse_native.check(handle.mbnb_colrow_quantize(ptr(t), dcode, R, C, ptr(q), ptr(rs), ptr(cs), ptr(ws), ws_bytes,
+                                                         stream_ptr(t.device)), "quantize_colrow")
+    return q, rs, cs
+
+
+def dequantize_colrow(quantized: Tensor, row_scales: Tensor, col_scales: Tensor, dtype: torch.dtype = torch.float16) -> Tensor:
+    """Dequantize INT8 with column + row statistics (reference: functional.py:927-932):
+    ``(q.float() * (sqrt(row_scales[:, None] * col_scales[None, :]) / 127.0)).to(dtype)``."""
+    if quantized.dim() != 2:
+        raise ValueError("Input must be 2D")
+    _check_device(quantized, "dequantize_colrow")
+    q = _as(quantized, torch.int8)
+    R, C = q.shape
+    rs = _f32_vector(row_scales, R, "row_scales", q.device)
+    cs = _f32_vector(col_scales, C, "col_scales", q.device)
+    dcode = dtype_code(dtype, "dequantize_colrow")
+    out = torch.empty((R, C), dtype=dtype, device=q.device)
+    with on_device(q.device):
+        _sparse_native.check(_sparse_native.lib().mbnb_colrow_dequantize(ptr(q), ptr(rs), ptr(cs), R, C, dcode, ptr(out), stream_ptr(q.device)),
+                             "dequantize_colrow")
+    return out
+
+
+def _matmul_colrow(input: Tensor, weight_int8: Tensor, weight_row_scales: Tensor, weight_col_scales: Tensor, bias: Optional[Tensor],
+                   dtype: torch.dtype, flags: int = 0) -> Tensor:
+    _check_device(input, "matmul_colrow")
+    _check_device(weight_int8, "matmul_colrow")
+    if weight_int8.dim() != 2:
+        raise ValueError("weight_int8 must be 2D")
+    dcode = dtype_code(dtype, "matmul_colrow")
+    N, K = weight_int8.shape
+    if input.shape[-1] != K:
+        raise RuntimeError(f"matmul_colrow: input width {input.shape[-1]} does not match weight {tuple(weight_int8.shape)}")
+    x = _as(input.reshape(-1, K), dtype)
+    M = x.shape[0]
+    w = _as(weight_int8, torch.int8)
+    rs = _f32_vector(weight_row_scales, N, "weight_row_scales", x.device)
+    cs = _f32_vector(weight_col_scales, K, "weight_col_scales", x.device)
+    b = None if bias is None else _as(bias, dtype, x.device)
+    if b is not None and b.numel() != N:
+        raise ValueError(f"bias has {b.numel()} elements, expected {N}")
+    out = torch.empty(M, N, dtype=dtype, device=x.device)
+    handle = _sparse_native.lib()
+    ws_bytes = int(handle.mbnb_colrow_matmul_workspace_bytes(M, N, K, dcode))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None
+    with on_device(x.device):
+        _sparse_native.check(handle.mbnb_colrow_matmul(ptr(x), dcode, M, K, ptr(w), ptr(rs), ptr(cs), N, ptr(b), ptr(out), ptr(ws), ws_bytes,
+                                                       int(flags), stream_ptr(x.device)), "matmul_colrow")
+    return out.reshape(*input.shape[:-1], N)
+
+
+def _colrow_dequant_pass(weight_int8: Tensor, weight_row_scales: Tensor, weight_col_scales: Tensor, dtype: torch.dtype) -> Tensor:
+    """matmul_colrow's first pass on its own, as its dense route runs it (write-through stores): Wd [N, K] in `dtype`, the bits its GEMM
+    reads.  For tests and tools."""
+    _check_device(weight_int8, "_colrow_dequant_pass")
+    w = _as(weight_int8, torch.int8)
+    N, K = w.shape
+    rs = _f32_vector(weight_row_scales, N, "weight_row_scales", w.device)
+    cs = _f32_vector(weight_col_scales, K, "weight_col_scales", w.device)
+    dcode = dtype_code(dtype, "_colrow_dequant_pass")
+    out = torch.empty(N, K, dtype=dtype, device=w.device)
+    with on_device(w.device):
+        _sparse_native.check(_sparse_native.lib().mbnb_colrow_matmul(None, dcode, 0, K, ptr(w), ptr(rs), ptr(cs), N, None, ptr(out), None, 0,
+                                                                     _sparse_native.PASS_ONLY, stream_ptr(w.device)), "_colrow_dequant_pass")
+    return out
+
+
+def matmul_colrow(input: Tensor, weight_int8: Tensor, weight_row_scales: Tensor, weight_col_scales: Tensor,
+                  bias: Optional[Tensor] = None, dtype: torch.dtype = torch.float16) -> Tensor:
+    """
+    ``input[..., K].to(dtype) @ dequantize_colrow(weight_int8[N, K], ..., dtype)^T + bias.to(dtype)`` (reference: functional.py:935-945):
+    f32 accumulation and one rounding to `dtype` with the bias inside it, as ``linear_dense``.  Inputs of any leading dims, 1-D included.
+
+    Inference only: the call records no autograd graph (the reference's gradient would flow through torch's F.linear on a weight that
+    is rebuilt from the int8 codes on every call; nothing trains through it).
+    """
+    return _matmul_colrow(input, weight_int8, weight_row_scales, weight_col_scales, bias, dtype)
+
+
+# ============================================================================= sparse COO (the outlier half of LLM.int8)
+# reference functional.py:952-1037 and its native CSR kernels (csrc/mps_bitsandbytes.mm:1598-1650, host :2585-2720), on libmbnb_sparse.so.
+_INDEX_BITS = {torch.int64: 64, torch.int32: 32}
+
+
+def _coo_row_ptr(tensor: Tensor, threshold: float) -> Tuple[Tensor, float, Tensor]:
+    """sparse_coo_from_dense's first launch pair: (the contiguous tensor, the threshold as the kernels take it, row_ptr int64 [rows + 1]) --
+    the exclusive scan of the per-row counts of kept elements, row_ptr[rows] the total."""
+    _check_device(tensor, "sparse_coo_from_dense")
+    rows, cols = tensor.shape
+    t = tensor if tensor.is_contiguous() else tensor.contiguous()
+    dcode = dtype_code(t.dtype, "sparse_coo_from_dense")
+    # `tensor.abs() >= threshold` compares in the tensor's dtype: the Python scalar is rounded to it first
+    thr = float(torch.tensor(float(threshold), dtype=t.dtype)) if threshold > 0 else 0.0
+    row_ptr = torch.empty(rows + 1, dtype=torch.int64, device=t.device)
+    with on_device(t.device):
+        _sparse_native.check(_sparse_native.lib().mbnb_coo_count(ptr(t), dcode, rows, cols, thr, ptr(row_ptr), stream_ptr(t.device)),
+                             "sparse_coo_from_dense")
+    return t, thr, row_ptr
+
+
+def sparse_coo_from_dense(tensor: Tensor, threshold: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, int, int]:
+    """
+    Convert a dense matrix to COO (reference: functional.py:1005-1020): (row int64 [nnz], col int64 [nnz], values [nnz] in the tensor's
+    dtype, rows, cols), entries in row-major order.  With ``threshold > 0`` elements with ``|x| < threshold`` are dropped, compared in
+    the tensor's dtype as torch compares them.  -0.0 is dropped, Inf and NaN are kept.
+
+    The size of the result depends on the data: one 8-byte read of the count between the two launches is the op's only host
+    synchronisation (what ``torch.nonzero`` does too).
+    """
+    rows, cols = tensor.shape
+    t, thr, row_ptr = _coo_row_ptr(tensor, threshold)
+    handle = _sparse_native.lib()
+    with on_device(t.device):
+        nnz = int(row_ptr[rows].item())
+        row = torch.empty(nnz, dtype=torch.int64, device=t.device)
+        col = torch.empty(nnz, dtype=torch.int64, device=t.device)
+        values = torch.empty(nnz, dtype=t.dtype, device=t.device)
+        _sparse_native.check(handle.mbnb_coo_fill(ptr(t), dtype_code(t.dtype, "sparse_coo_from_dense"), rows, cols, thr, ptr(row_ptr), ptr(row),
+                                                  ptr(col), ptr(values), nnz, stream_ptr(t.device)), "sparse_coo_from_dense")
+    return row, col, values, rows, cols
+
+
+def quantize_sparse_coo(row_indices: Tensor, col_indices: Tensor, values: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """
+    Quantize COO values to INT8 with one absmax scale (reference: functional.py:1023-1037): ``scale = max(|v|).clamp(1e-8) / 127``,
+    ``q = clamp(round(v / scale), -127, 127)``.  Returns (row_indices, col_indices, int8 [nnz], scale f32 [1]); the indices are
+    returned as given.  The maximum never leaves the device.
+    """
+    _check_device(values, "quantize_sparse_coo")
+    if values.numel() == 0:
+        raise RuntimeError("quantize_sparse_coo: values is empty (nnz == 0): the maximum of no elements is undefined")
+    v = values if values.is_contiguous() else values.contiguous()
+    dcode = dtype_code(v.dtype, "quantize_sparse_coo")
+    q = torch.empty(v.shape, dtype=torch.int8, device=v.device)
+    scale = torch.empty(1, dtype=torch.float32, device=v.device)
+    handle = _sparse_native.lib()
+    ws_bytes = int(handle.mbnb_coo_quantize_workspace_bytes())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device)
+    with on_device(v.device):
+        _sparse_native.check(handle.mbnb_coo_quantize(ptr(v), dcode, v.numel(), ptr(q), ptr(scale), ptr(ws), ws_bytes, stream_ptr(v.device)),
+                             "quantize_sparse_coo")
+    return row_indices, col_indices, q, scale
+
+
+def _spmm_coo(row_indices: Tensor, col_indices: Tensor, values: Tensor, kind: int, scale: Optional[Tensor], dense: Tensor, sparse_rows: int,
+              sparse_cols: int, dtype: torch.dtype, what: str, flags: int = 0) -> Tensor:
+    """Validation and the call of mbnb_spmm_coo.  `flags`: include/mbnb_sparse.h, for tests."""
+    if row_indices.dim() != 1 or col_indices.dim() != 1 or values.dim() != 1:
+        raise ValueError(f"{what}: row_indices, col_indices and values must be 1-D")
+    nnz = values.numel()
+    if row_indices.numel() != nnz or col_indices.numel() != nnz:
+        raise ValueError(f"{what}: row_indices ({row_indices.numel()}), col_indices ({col_indices.numel()}) and values ({nnz}) differ in length")
+    if row_indices.dtype not in _INDEX_BITS or col_indices.dtype not in _INDEX_BITS:
+        raise ValueError(f"{what}: indices must be int64 or int32, got {row_indices.dtype} and {col_indices.dtype}")
+    if dense.dim() != 2:
+        raise ValueError(f"{what}: dense must be 2-D, got {dense.dim()}-D")
+    sparse_rows, sparse_cols = int(sparse_rows), int(sparse_cols)
+    if sparse_rows < 0 or sparse_cols < 0:
+        raise ValueError(f"{what}: negative sparse shape ({sparse_rows}, {sparse_cols})")
+    if dense.shape[0] != sparse_cols:
+        raise ValueError(f"{what}: dense has {dense.shape[0]} rows, the sparse matrix {sparse_cols} columns")
+    if dense.dtype != dtype:
+        raise ValueError(f"{what}: dense is {dense.dtype}, the sparse values are {dtype}")
+    _check_device(values, what)
+    _check_device(dense, what)
+    dev = dense.device
+    dcode = dtype_code(dtype, what)
+    r = row_indices.to(dev).contiguous()
+    c = col_indices.to(dev).contiguous()
+    v = values.to(dev).contiguous()
+    d = dense if dense.is_contiguous() else dense.contiguous()
+    N = d.shape[1]
+    out = torch.empty(sparse_rows, N, dtype=dtype, device=dev)
+    handle = _sparse_native.lib()
+    ws_bytes = int(handle.mbnb_spmm_coo_workspace_bytes(nnz, sparse_rows))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    with on_device(dev):
+        _sparse_native.check(handle.mbnb_spmm_coo(ptr(r), _INDEX_BITS[r.dtype], ptr(c), _INDEX_BITS[c.dtype], ptr(v), kind, ptr(scale), nnz, ptr(d),
+                                                  dcode, sparse_rows, sparse_cols, N, ptr(out), ptr(ws), ws_bytes, int(flags), stream_ptr(dev)), what)
+    return out
+
+
+def spmm_coo(row_indices: Tensor, col_indices: Tensor, values: Tensor, dense: Tensor, sparse_rows: int, sparse_cols: int) -> Tensor:
+    """
+    ``sparse @ dense`` with the sparse matrix in COO form (reference: functional.py:952-979; native binding `_C.spmm_coo`): the result
+    is [sparse_rows, N] in ``values.dtype``, each element one f32 sum rounded once.  Indices may be int64 or int32, in any order;
+    duplicates add.  The same inputs give the same bits on every call.
+
+    Unlike the reference, which raises, an entry whose row or column index is outside the sparse shape is skipped: a bounds check
+    that raises would cost a device synchronisation.  Nothing outside any buffer is read or written.
+    """
+    return _spmm_coo(row_indices, col_indices, values, _sparse_native.COO_VALUES, None, dense, sparse_rows, sparse_cols, values.dtype, "spmm_coo")
+
+
+def spmm_coo_int8(row_indices: Tensor, col_indices: Tensor, values_int8: Tensor, values_scale: Tensor, dense: Tensor, sparse_rows: int,
+                  sparse_cols: int, dtype: torch.dtype = torch.float16) -> Tensor:
+    """
+    ``spmm_coo`` with INT8 values (reference: functional.py:982-1002; native binding `_C.spmm_coo_int8`): each value is
+    ``values_int8.to(dtype) * scale`` with a one-element ``values_scale``, or ``values_int8.to(dtype) * values_scale.to(dtype)`` with one scale
+    per entry; ``dense`` is cast to `dtype`.  Out-of-range indices are skipped as in ``spmm_coo``.
+    """
+    if values_int8.dtype != torch.int8:
+        raise ValueError(f"spmm_coo_int8: values_int8 must be int8, got {values_int8.dtype}")
+    nnz = values_int8.numel()
+    if values_scale.numel() == 1:
+        kind = _sparse_native.COO_INT8_SCALAR
+    elif values_scale.numel() == nnz:
+        kind = _sparse_native.COO_INT8_ENTRY
+    else:
+        raise ValueError(f"spmm_coo_int8: values_scale has {values_scale.numel()} elements, expected 1 or {nnz}")
+    _check_device(dense, "spmm_coo_int8")
+    dtype_code(dtype, "spmm_coo_int8")
+    scale = _as(values_scale, torch.float32, dense.device).reshape(-1)
+    return _spmm_coo(row_indices, col_indices, values_int8, kind, scale, _as(dense, dtype), sparse_rows, sparse_cols, dtype, "spmm_coo_int8")
 
 
 # ============================================================================= quantized embedding lookups
