@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.goldenio import DT, from_bits
+from tests import optim_emul as emul
+from tests.goldenio import DT, NAME, from_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,9 @@ def test_golden_step_by_step(g10, cid):
     codes and maxima are the reference's bits.  Two documented exceptions: f32 parameters under Adam may
     be 1 ulp away (torch's vectorised CPU sqrt is not correctly rounded; the kernel's is), and SGD's 16-bit parameters
     may be 1 ulp away in the last numel % 64 elements (torch's scalar tail loop rounds alpha * x to 16 bits first).
-    The max_grad_norm case clips on the GPU, whose norm differs from the CPU's in the last bits: compared within a tolerance."""
+    The max_grad_norm case clips on the GPU, whose norm differs from the CPU's in the last bits: compared within a tolerance
+    against the golden, and bit for bit against the emulation (tests/optim_emul.py) fed the clipped gradient that p.grad holds
+    after the step."""
     from mps_bitsandbytes_amd import synthetic
     man, z = g10
     case = man["g10"][cid]
@@ -83,7 +86,23 @@ def test_golden_step_by_step(g10, cid):
             else:
                 p.grad = synthetic.normal(shapes[j], gdt, seed=seed + 100 * j + s).to(DEV)
                 nsteps[j] += 1
+        emus = []
+        if clip:                     # the emulation starts each step where the GPU does: the golden's parameter and state
+            for j, p in enumerate(params):
+                e = emul.EmuTensor(case["opt"], {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2, **case["kwargs"]}, p.detach(),
+                                   case["kwargs"].get("block_size", 256))
+                st = opt.state[p]
+                if st:
+                    e.q1, e.a1, e.q2, e.a2 = (st[k].detach().cpu().flatten().numpy().copy() for k in keys)
+                    e.step_count = st["step"]
+                emus.append(e)
         opt.step()
+        for e, p in zip(emus, params):
+            if p.grad is not None:
+                e.step(p.grad)       # clip_grad_norm_ scaled p.grad in place: this is the gradient the kernel read
+                st = opt.state[p]
+                emul.compare(f"case {cid} step {s} against the emulation", dict(zip(("q1", "a1", "q2", "a2"), (st[k] for k in keys)), p=p.detach()),
+                             e.result(), e.bs, NAME[pdt], e.before)
         for j, p in enumerate(params):
             want = from_bits(z[f"c{cid}_p{j}_s{s}"], pdt).view(shapes[j])
             got = p.detach().cpu()
@@ -309,7 +328,9 @@ def _restated_adamw_step(p, g, st, lr, b1, b2, eps, wd, bs):
 
 def test_qlora_adamw8bit_end_to_end():
     """A frozen NF4 base plus rank-16 adapters trained for 20 steps with AdamW8bit: the loss falls, the base's buffers
-    do not change, and the adapters stay within 5e-2 (relative Frobenius) of the same loop under the f32 restatement."""
+    do not change, and the adapters stay within 5e-2 (relative Frobenius) of the same loop under the f32 restatement.  The
+    emulation (tests/optim_emul.py), fed each step's GPU gradients and chained from its own state, must hold the adapters, the
+    codes and the maxima bit for bit after the 20 steps."""
     import mps_bitsandbytes_amd as bnb
     from mps_bitsandbytes_amd import synthetic
     optim = _optim()
@@ -336,6 +357,8 @@ def test_qlora_adamw8bit_end_to_end():
 
     A, B = adapters()
     opt = optim.AdamW8bit([A, B], lr=5e-3)
+    hp = dict(lr=5e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    emus = [emul.EmuTensor("adamw", hp, t.detach(), 256) for t in (A, B)]
     A2, B2 = adapters()
     states = [dict(m=torch.zeros(t.numel(), dtype=torch.int8, device=DEV), ma=torch.full((-(-t.numel() // 256),), 1e-8, device=DEV),
                    v=torch.zeros(t.numel(), dtype=torch.uint8, device=DEV), vm=torch.full((-(-t.numel() // 256),), 1e-12, device=DEV), t=0)
@@ -346,6 +369,8 @@ def test_qlora_adamw8bit_end_to_end():
         loss = loss_of(A, B)
         loss.backward()
         opt.step()
+        for e, t in zip(emus, (A, B)):
+            e.step(t.grad)
         losses.append(loss.item())
         A2.grad = B2.grad = None
         loss_of(A2, B2).backward()
@@ -358,3 +383,7 @@ def test_qlora_adamw8bit_end_to_end():
     for t, t2 in zip((A, B), (A2, B2)):
         err = ((t.float() - t2.float()).norm() / t2.float().norm()).item()
         assert err < 5e-2, err
+    for name, e, t in zip("AB", emus, (A, B)):
+        st = opt.state[t]
+        got = dict(p=t.detach(), q1=st["exp_avg_int8"], a1=st["exp_avg_absmax"], q2=st["exp_avg_sq_uint8"], a2=st["exp_avg_sq_max"])
+        emul.compare(f"adapter {name} after 20 steps", got, e.result(), 256, "bf16", e.before)
