@@ -64,8 +64,9 @@ enum {
 int mbnb_abi_version(void);
 /* thread-local, never NULL; valid until the next failing call on this thread */
 const char *mbnb_last_error(void);
-/* name of the kernel family the last mbnb_matmul_4bit / mbnb_linear_int8 call on this thread
- * dispatched to ("gemv", "mfma128", "generic", ...) — for tests and the bench driver */
+/* name of the kernel family the last call on this thread dispatched to ("gemv", "mfma128", "generic", ...; the quantise /
+ * dequantise entry points report the form their launcher took: "q4_rows2", "dq4_flat", "q8_row_regs", "dquant8_rc", ...,
+ * DESIGN.md §13) — for tests and the bench driver */
 const char *mbnb_last_kernel(void);
 
 /* ---------------------------------------------------------------------------

@@ -366,11 +366,14 @@ __global__ __launch_bounds__(256) void k_quantize_4bit_tiny(const T *__restrict_
         if (absmax_in) am = absmax_in[r * nblk + blk];
         else {
             am = 0.0f;
+            bool nan = false;
             for (int i = 0; i < blocksize; i++) {
                 int64_t kk = blk * blocksize + i;
-                am = fmaxf(am, kk < cols ? fabsf(to_f32(A[r * cols + kk])) : 0.0f);
+                const float v = kk < cols ? to_f32(A[r * cols + kk]) : 0.0f;
+                am = fmaxf(am, fabsf(v));
+                nan |= (v != v);
             }
-            am = fmaxf(am, 1e-8f);
+            am = nan ? __builtin_bit_cast(float, 0x7FC00000u) : fmaxf(am, 1e-8f);   // abs().max() propagates NaN (fmaxf drops it), as block_absmax8
         }
         if (k % blocksize == 0) absmax_out[r * nblk + blk] = am;
         float x = k < cols ? to_f32(A[r * cols + k]) : 0.0f;
@@ -525,6 +528,7 @@ int dequant_absmax_dispatch(const void *q, int q_kind, int64_t rows, int64_t num
         case 1: hipLaunchKernelGGL(k_dequant_absmax<1>, dim3(grid), dim3(256), 0, st, q, rows, num_blocks, scales, dq_blocks, blocksize, out); break;
         default: hipLaunchKernelGGL(k_dequant_absmax<2>, dim3(grid), dim3(256), 0, st, q, rows, num_blocks, scales, dq_blocks, blocksize, out); break;
     }
+    set_kernel_name(q_kind == 0 ? "dequant_absmax_i8" : (q_kind == 1 ? "dequant_absmax_u8" : "dequant_absmax_f32"));
     return check_launch("dequant_absmax");
 }
 
@@ -918,6 +922,7 @@ static int launch_quantize_4bit(const void *A, int64_t rows, int64_t cols, int64
         else
             hipLaunchKernelGGL((k_quantize_4bit_tiny<T, MBNB_FP4>), dim3(grid), dim3(256), 0, st, a, rows, cols,
                                cols_padded, blocksize, absmax_in, packed, absmax_out);
+        set_kernel_name("q4_tiny");
         return check_launch("quantize_4bit(tiny)");
     }
     const bool vec_ok = aligned16(A) && (cols % 8 == 0);
@@ -941,6 +946,14 @@ static int launch_quantize_4bit(const void *A, int64_t rows, int64_t cols, int64
         else MBNB_Q4(MBNB_FP4, 1);
     }
 #undef MBNB_Q4
+    // the form that ran: tiny (above) | big (blocks of more than one 512-element wave step, two passes) | wave (flat wave index) |
+    // rows (one grid row per matrix row) | rows2 (the same, two spans per wave); "_s": 2- / 4-byte loads (A not 16-byte aligned or cols % 8)
+    if (blocksize > 512) {
+        if (row_grid) set_kernel_name(vec_ok ? "q4_big_rows" : "q4_big_rows_s");
+        else set_kernel_name(vec_ok ? "q4_big" : "q4_big_s");
+    } else if (two) set_kernel_name(vec_ok ? "q4_rows2" : "q4_rows2_s");
+    else if (row_grid) set_kernel_name(vec_ok ? "q4_rows" : "q4_rows_s");
+    else set_kernel_name(vec_ok ? "q4_wave" : "q4_wave_s");
     return check_launch("quantize_4bit");
 }
 
@@ -957,6 +970,7 @@ static int launch_quantize_4bit_dq(const void *A, int64_t rows, int64_t cols, in
     else
         hipLaunchKernelGGL((k_quantize_4bit_dq<T, MBNB_FP4>), dim3(grid), dim3(256), 0, st, a, rows, cols, cols_padded, blocksize,
                            packed, am_codes, absmax2, vec_ok);
+    set_kernel_name(vec_ok ? "q4_dq" : "q4_dq_s");
     return check_launch("quantize_4bit(dq)");
 }
 
@@ -1093,6 +1107,7 @@ static int launch_dequantize_4bit(const uint8_t *packed, const AbsmaxView &am, i
                 if (am.i8) hipLaunchKernelGGL((k_dequantize_4bit_flat<T, QT, true, 1>), grid, dim3(256), 0, st, packed, am, ndw, sh, static_cast<T *>(out), store_policy);
                 else hipLaunchKernelGGL((k_dequantize_4bit_flat<T, QT, false, 1>), grid, dim3(256), 0, st, packed, am, ndw, sh, static_cast<T *>(out), store_policy);
             }
+            set_kernel_name("dq4_flat");   // every store policy: the composites that pass 1 or 2 report their own name after this pass
             return check_launch("dequantize_4bit");
         }
     }
@@ -1107,6 +1122,9 @@ static int launch_dequantize_4bit(const uint8_t *packed, const AbsmaxView &am, i
     else
         hipLaunchKernelGGL((k_dequantize_4bit<T, QT, false>), grid, dim3(256), 0, st, packed, am, rows, cols,
                            cols_padded, blocksize, static_cast<T *>(out), vec_ok, row_grid);
+    // "_s": element stores (out not 16-byte aligned or cols % 8)
+    if (row_grid) set_kernel_name(vec_ok ? "dq4_rows" : "dq4_rows_s");
+    else set_kernel_name(vec_ok ? "dq4_plain" : "dq4_plain_s");
     return check_launch("dequantize_4bit");
 }
 
@@ -1137,6 +1155,7 @@ int quantize_blockwise_dispatch(const void *A, int dtype, int64_t numel, int blo
         case MBNB_BF16: hipLaunchKernelGGL(k_quantize_blockwise<bf16_t>, dim3(grid), dim3(256), 0, st, static_cast<const bf16_t *>(A), numel, blocksize, absmax_in, out, absmax_out); break;
         default: hipLaunchKernelGGL(k_quantize_blockwise<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(A), numel, blocksize, absmax_in, out, absmax_out); break;
     }
+    set_kernel_name("q8_block");
     return check_launch("quantize_blockwise");
 }
 
@@ -1152,6 +1171,7 @@ int dequantize_blockwise_dispatch(const int8_t *q, int64_t numel, const float *a
         case MBNB_BF16: hipLaunchKernelGGL(k_dequantize_blockwise<bf16_t>, dim3(grid), dim3(256), 0, st, q, numel, absmax, blocksize, static_cast<bf16_t *>(out)); break;
         default: hipLaunchKernelGGL(k_dequantize_blockwise<float>, dim3(grid), dim3(256), 0, st, q, numel, absmax, blocksize, static_cast<float *>(out)); break;
     }
+    set_kernel_name("dq8_block");
     return check_launch("dequantize_blockwise");
 }
 
@@ -1162,6 +1182,7 @@ int quantize_rowwise_dispatch(const void *A, int dtype, int64_t rows, int64_t co
     if (vec_ok && cols <= 8192 && dtype != MBNB_F32) {   // the row fits the registers of one workgroup: one pass over memory
         if (dtype == MBNB_F16) hipLaunchKernelGGL(k_quantize_rowwise_regs<f16_t>, dim3(grid), dim3(256), 0, st, static_cast<const f16_t *>(A), cols, out, scales);
         else hipLaunchKernelGGL(k_quantize_rowwise_regs<bf16_t>, dim3(grid), dim3(256), 0, st, static_cast<const bf16_t *>(A), cols, out, scales);
+        set_kernel_name("q8_row_regs");
         return check_launch("quantize_rowwise");
     }
     switch (dtype) {
@@ -1169,6 +1190,7 @@ int quantize_rowwise_dispatch(const void *A, int dtype, int64_t rows, int64_t co
         case MBNB_BF16: hipLaunchKernelGGL(k_quantize_rowwise<bf16_t>, dim3(grid), dim3(256), 0, st, static_cast<const bf16_t *>(A), rows, cols, out, scales, vec_ok); break;
         default: hipLaunchKernelGGL(k_quantize_rowwise<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(A), rows, cols, out, scales, vec_ok); break;
     }
+    set_kernel_name(vec_ok ? "q8_row_loop" : "q8_row_scalar");
     return check_launch("quantize_rowwise");
 }
 
@@ -1180,11 +1202,13 @@ int quantize_fp8_dispatch(const void *A, int dtype, int64_t rows, int64_t cols, 
         case MBNB_BF16: hipLaunchKernelGGL(k_quantize_fp8<bf16_t>, dim3(grid), dim3(256), 0, st, static_cast<const bf16_t *>(A), rows, cols, out, scales, vec_ok); break;
         default: hipLaunchKernelGGL(k_quantize_fp8<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(A), rows, cols, out, scales, vec_ok); break;
     }
+    set_kernel_name(vec_ok ? "qfp8_row_loop" : "qfp8_row_scalar");
     return check_launch("quantize_fp8_e4m3");
 }
 
 int dequantize_fp8_dispatch(const uint8_t *q, const float *scales, int64_t rows, int64_t cols, int out_dtype, void *out,
                             hipStream_t st, int store_policy) {
+    // store policies 1 and 2 (inside fp8a16_dequant+dense* only, which reports its own name after this pass)
     if (launch_rows8_wt<true>(q, scales, rows, cols, out_dtype, out, st, store_policy)) return check_launch("dequantize_fp8_e4m3");
     if (cols % 16 == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && rows * cols > 0 && rows < 65536) {
         const dim3 g16((unsigned)((cols / 16 + 255) / 256), (unsigned)rows);
@@ -1193,6 +1217,7 @@ int dequantize_fp8_dispatch(const uint8_t *q, const float *scales, int64_t rows,
             case MBNB_BF16: hipLaunchKernelGGL((k_dequantize_rows16<bf16_t, true>), dim3(g16), dim3(256), 0, st, q, scales, rows, cols, static_cast<bf16_t *>(out)); break;
             default: hipLaunchKernelGGL((k_dequantize_rows16<float, true>), dim3(g16), dim3(256), 0, st, q, scales, rows, cols, static_cast<float *>(out)); break;
         }
+        set_kernel_name("dqfp8_rows16");
         return check_launch("dequantize_fp8_e4m3");
     }
     const unsigned grid = (unsigned)((rows * cols + 255) / 256);
@@ -1201,11 +1226,13 @@ int dequantize_fp8_dispatch(const uint8_t *q, const float *scales, int64_t rows,
         case MBNB_BF16: hipLaunchKernelGGL(k_dequantize_fp8<bf16_t>, dim3(grid), dim3(256), 0, st, q, scales, rows, cols, static_cast<bf16_t *>(out)); break;
         default: hipLaunchKernelGGL(k_dequantize_fp8<float>, dim3(grid), dim3(256), 0, st, q, scales, rows, cols, static_cast<float *>(out)); break;
     }
+    set_kernel_name("dqfp8_scalar");
     return check_launch("dequantize_fp8_e4m3");
 }
 
 int dequantize_rowwise_dispatch(const int8_t *q, const float *scales, int64_t rows, int64_t cols, int out_dtype,
                                 void *out, hipStream_t st, int store_policy) {
+    // store policies 1 and 2 (inside w8a16_dequant+dense* only, which reports its own name after this pass)
     if (launch_rows8_wt<false>(reinterpret_cast<const uint8_t *>(q), scales, rows, cols, out_dtype, out, st, store_policy)) return check_launch("dequantize_rowwise");
     if (cols % 16 == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && rows * cols > 0 && rows < 65536) {
         const dim3 g16((unsigned)((cols / 16 + 255) / 256), (unsigned)rows);
@@ -1215,6 +1242,7 @@ int dequantize_rowwise_dispatch(const int8_t *q, const float *scales, int64_t ro
             case MBNB_BF16: hipLaunchKernelGGL((k_dequantize_rows16<bf16_t, false>), dim3(g16), dim3(256), 0, st, qb, scales, rows, cols, static_cast<bf16_t *>(out)); break;
             default: hipLaunchKernelGGL((k_dequantize_rows16<float, false>), dim3(g16), dim3(256), 0, st, qb, scales, rows, cols, static_cast<float *>(out)); break;
         }
+        set_kernel_name("dq8_rows16");
         return check_launch("dequantize_rowwise");
     }
     const unsigned grid = (unsigned)((rows * cols + 255) / 256);
@@ -1223,6 +1251,7 @@ int dequantize_rowwise_dispatch(const int8_t *q, const float *scales, int64_t ro
         case MBNB_BF16: hipLaunchKernelGGL(k_dequantize_rowwise<bf16_t>, dim3(grid), dim3(256), 0, st, q, scales, rows, cols, static_cast<bf16_t *>(out)); break;
         default: hipLaunchKernelGGL(k_dequantize_rowwise<float>, dim3(grid), dim3(256), 0, st, q, scales, rows, cols, static_cast<float *>(out)); break;
     }
+    set_kernel_name("dq8_scalar");
     return check_launch("dequantize_rowwise");
 }
 
@@ -1242,6 +1271,8 @@ static int launch_double_quant(const void *A, int64_t rows, int64_t cols, int8_t
         }
         hipLaunchKernelGGL(k_double_quant8<T>, dim3(gx, (unsigned)((rows + 7) / 8)), dim3(256), 0, st, a, rows, cols, col_stats,
                            row_stats, out_col, out_row, !col_given, !row_given);
+        // the statistics this call computed: rc both, r / c the rows' / the columns' only, given neither
+        set_kernel_name(row_given ? (col_given ? "dquant8_given" : "dquant8_c") : (col_given ? "dquant8_r" : "dquant8_rc"));
         return check_launch("double_quant");
     }
     if (!row_given) hipLaunchKernelGGL(k_row_absmax<T>, dim3((unsigned)rows), dim3(256), 0, st, a, rows, cols, row_stats);
@@ -1257,6 +1288,7 @@ static int launch_double_quant(const void *A, int64_t rows, int64_t cols, int8_t
     }
     hipLaunchKernelGGL(k_double_quant<T>, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, st, a, rows, cols,
                        col_stats, row_stats, out_col, out_row);
+    set_kernel_name(row_given ? (col_given ? "dquant1_given" : "dquant1_c") : (col_given ? "dquant1_r" : "dquant1_rc"));
     return check_launch("double_quant");
 }
 

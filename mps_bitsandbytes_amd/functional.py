@@ -246,8 +246,10 @@ def quantize_4bit(
     nblocks = rows * cols_padded // blocksize
 
     user_out = out
+    # the kernels store whole dwords: a caller's buffer off a 4-byte boundary (a contiguous view at an odd storage offset) is
+    # filled by the copy below, as any other `out` that cannot be written directly
     if (out is not None and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
-            and out.device == A.device):
+            and out.device == A.device and out.data_ptr() % 4 == 0):
         packed = out.view(-1)
     else:
         packed = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
@@ -329,6 +331,8 @@ def dequantize_4bit(
     A = A.contiguous()
     if A.dtype != torch.uint8:
         A = A.to(torch.uint8)
+    if A.data_ptr() % 4 != 0:
+        A = A.clone()       # the kernels read whole dwords: a contiguous view at an odd storage offset is copied to a fresh allocation
     if shape is not None and len(shape) == 2:
         rows, cols = int(shape[0]), int(shape[1])
         cols_padded = _padded(cols, blocksize)

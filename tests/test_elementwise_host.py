@@ -9,7 +9,7 @@ import re
 import pytest
 import torch
 
-from tests import kernel_cases
+from tests import kernel_cases, quant_cases
 from tests.elementwise import assert_linear_elementwise, expected_nonfinite
 from tests.goldenio import rel_fro
 
@@ -113,11 +113,13 @@ def test_nonfinite_values_stay_in_their_row_and_column():
 
 
 # ----------------------------------------------------------------------------------------------- closure over the kernel names
-def _reported_names():
-    """(names, prefixes): every string literal passed to set_kernel_name in csrc/*.hip and *.h, and for a formatted name the text of
-    its snprintf format before the first conversion."""
+def _reported_names(only=None):
+    """(names, prefixes): every string literal passed to set_kernel_name in csrc/*.hip and *.h (`only`: in that file alone), and for a
+    formatted name the text of its snprintf format before the first conversion."""
     names, prefixes = set(), set()
     for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
+        if only is not None and os.path.basename(path) != only:
+            continue
         with open(path) as f:
             src = f.read()
         for m in re.finditer(r"\bset_kernel_name\(", src):
@@ -146,7 +148,7 @@ def test_the_name_scan_sees_the_library():
 
 def test_every_reported_kernel_name_is_the_kernel_of_a_case():
     names, prefixes = _reported_names()
-    expected = {c["kernel"] for c in kernel_cases.CASES}
+    expected = {c["kernel"] for c in kernel_cases.CASES} | {c["form"] for c in quant_cases.CASES}
     assert sorted((names | prefixes) - expected) == []
     assert sorted(expected - (names | prefixes)) == [], "a case names a kernel the library never reports"
 
