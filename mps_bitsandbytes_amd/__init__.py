@@ -26,6 +26,8 @@ from .functional import (
 )
 from .nn import (Linear4bit, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
                  OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback)
+from .optim import (Adam8bit, AdamW8bit, Lion8bit, SGD8bit, PagedAdam, PagedAdamW, PagedLion,
+                    quantize_state, dequantize_state)
 from .integration import (
     BitsAndBytesConfig, quantize_model, replace_linear_with_4bit, replace_linear_with_8bit, get_memory_footprint,
 )
@@ -57,5 +59,6 @@ __all__ = [
     'SwitchBackLinear', 'SwitchBackLinearCallback', 'switchback_linear', 'linear_grad_weight',
     'quantize_colrow', 'dequantize_colrow', 'matmul_colrow',
     'sparse_coo_from_dense', 'quantize_sparse_coo', 'spmm_coo', 'spmm_coo_int8',
+    'Adam8bit', 'AdamW8bit', 'Lion8bit', 'SGD8bit', 'PagedAdam', 'PagedAdamW', 'PagedLion', 'quantize_state', 'dequantize_state',
     'BitsAndBytesConfig', 'quantize_model', 'replace_linear_with_4bit', 'replace_linear_with_8bit', 'get_memory_footprint',
 ]
