@@ -66,7 +66,11 @@ int mbnb_abi_version(void);
 const char *mbnb_last_error(void);
 /* name of the kernel family the last call on this thread dispatched to ("gemv", "mfma128", "generic", ...; the quantise /
  * dequantise entry points report the form their launcher took: "q4_rows2", "dq4_flat", "q8_row_regs", "dquant8_rc", ...,
- * DESIGN.md §13) — for tests and the bench driver */
+ * DESIGN.md §13) — for tests and the bench driver.
+ * The pointer leads into a thread-local buffer that holds TWO strings: the name, its terminating NUL, then the VARIANT of the
+ * call's GEMM launch and a second NUL -- the kernel and its non-type template arguments or runtime branch ("gemv_lean ku5/KU6",
+ * "small MF8 NF2 S16 x3", "dense_nb 8/7", "generic ROWS8 flags3"), "" where the launcher sets none.  A reader of
+ * the name alone sees what it always saw; the variant is at `p + strlen(p) + 1`.  Valid until the next call on this thread. */
 const char *mbnb_last_kernel(void);
 
 /* ---------------------------------------------------------------------------

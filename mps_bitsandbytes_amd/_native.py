@@ -125,6 +125,19 @@ def last_kernel() -> str:
     return lib().mbnb_last_kernel().decode()
 
 
+_last_kernel_addr = None
+
+
+def last_variant() -> str:
+    """The variant of the last call's GEMM launch ("gemv_lean ku5/KU6", "dense_nb 8/7", ...; "" where the launcher sets none): the
+    second string of mbnb_last_kernel()'s buffer, right behind the name's terminating NUL (include/mbnb_hip.h)."""
+    global _last_kernel_addr
+    if _last_kernel_addr is None:
+        _last_kernel_addr = ctypes.CFUNCTYPE(c_void_p)(("mbnb_last_kernel", lib()))    # the same export, its pointer kept as an address
+    addr = _last_kernel_addr()
+    return ctypes.string_at(addr + len(ctypes.string_at(addr)) + 1).decode()
+
+
 def check(status: int, what: str) -> None:
     if status != 0:
         msg = lib().mbnb_last_error().decode(errors="replace")

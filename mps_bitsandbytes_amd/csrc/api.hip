@@ -4,6 +4,7 @@
 // idempotent function attributes below (mutex-protected), the error text is thread-local.
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 
@@ -13,7 +14,10 @@
 namespace mbnb {
 
 static thread_local char g_err[512] = "";
-static thread_local const char *g_kernel = "";
+// the last call's kernel name and the variant of its GEMM launch; mbnb_last_kernel() hands out both in one buffer (name, NUL, variant, NUL)
+static thread_local char g_kernel[64] = "";
+static thread_local char g_variant[64] = "";
+static thread_local char g_kernel_out[sizeof(g_kernel) + sizeof(g_variant)] = "";
 
 void set_error(const char *fmt, ...) {
     va_list ap;
@@ -21,7 +25,15 @@ void set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-void set_kernel_name(const char *name) { g_kernel = name; }
+void set_kernel_name(const char *name) { snprintf(g_kernel, sizeof(g_kernel), "%s", name); }
+void set_kernel_variant(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_variant, sizeof(g_variant), fmt, ap);
+    va_end(ap);
+}
+// every launching entry point begins with this: a call whose launcher sets no variant reports "", never the previous call's
+static void begin_call() { g_variant[0] = '\0'; }
 
 int ensure_dyn_lds(const void *func, int bytes, const char *what) {
     int dev = 0;
@@ -90,10 +102,16 @@ extern "C" {
 int mbnb_abi_version(void) { return MBNB_ABI_VERSION; }
 
 const char *mbnb_last_error(void) { return g_err; }
-const char *mbnb_last_kernel(void) { return g_kernel; }
+const char *mbnb_last_kernel(void) {
+    const size_t n = strlen(g_kernel) + 1;
+    memcpy(g_kernel_out, g_kernel, n);
+    memcpy(g_kernel_out + n, g_variant, strlen(g_variant) + 1);
+    return g_kernel_out;
+}
 
 int mbnb_quantize_4bit(const void *A, int dtype, int64_t rows, int64_t cols, int64_t cols_padded, int blocksize,
                        int quant_type, const float *absmax_in, uint8_t *packed, float *absmax_out, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype) || !qt_ok(quant_type)) return fail(MBNB_ERR_ARG, "quantize_4bit: bad dtype/quant_type");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "quantize_4bit: negative size");
     if (!pow2(blocksize) || blocksize > 65536)
@@ -110,6 +128,7 @@ int mbnb_quantize_4bit(const void *A, int dtype, int64_t rows, int64_t cols, int
 
 int mbnb_quantize_4bit_dq(const void *A, int dtype, int64_t rows, int64_t cols, int64_t cols_padded, int blocksize,
                           int quant_type, uint8_t *packed, int8_t *absmax_codes, float *absmax2, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype) || !qt_ok(quant_type)) return fail(MBNB_ERR_ARG, "quantize_4bit_dq: bad dtype/quant_type");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "quantize_4bit_dq: negative size");
     if (!pow2(blocksize) || blocksize < 8 || blocksize > 512)
@@ -127,6 +146,7 @@ int mbnb_quantize_4bit_dq(const void *A, int dtype, int64_t rows, int64_t cols, 
 
 int mbnb_dequantize_4bit(const uint8_t *packed, const mbnb_absmax *absmax, int64_t rows, int64_t cols,
                          int64_t cols_padded, int blocksize, int quant_type, int out_dtype, void *out, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype) || !qt_ok(quant_type)) return fail(MBNB_ERR_ARG, "dequantize_4bit: bad dtype/quant_type");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "dequantize_4bit: negative size");
     if (!pow2(blocksize) || blocksize > 65536) return fail(MBNB_ERR_ARG, "dequantize_4bit: bad blocksize %d", blocksize);
@@ -143,6 +163,7 @@ int mbnb_dequantize_4bit(const uint8_t *packed, const mbnb_absmax *absmax, int64
 
 int mbnb_quantize_blockwise(const void *A, int dtype, int64_t numel, int blocksize, const float *absmax_in,
                             int8_t *out, float *absmax_out, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "quantize_blockwise: bad dtype");
     if (numel < 0 || blocksize <= 0 || blocksize > 65536) return fail(MBNB_ERR_ARG, "quantize_blockwise: bad size");
     if (numel == 0) return MBNB_OK;
@@ -153,6 +174,7 @@ int mbnb_quantize_blockwise(const void *A, int dtype, int64_t numel, int blocksi
 
 int mbnb_dequantize_blockwise(const int8_t *q, int64_t numel, const float *absmax, int blocksize, int out_dtype,
                               void *out, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "dequantize_blockwise: bad dtype");
     if (numel < 0 || blocksize <= 0) return fail(MBNB_ERR_ARG, "dequantize_blockwise: bad size");
     if (numel == 0) return MBNB_OK;
@@ -162,6 +184,7 @@ int mbnb_dequantize_blockwise(const int8_t *q, int64_t numel, const float *absma
 
 int mbnb_dequant_absmax(const void *codes, int code_kind, int64_t rows, int64_t num_blocks, const float *scales,
                         int64_t dq_blocks, int blocksize, float *out, void *stream) {
+    begin_call();
     if (code_kind < 0 || code_kind > 2) return fail(MBNB_ERR_ARG, "dequant_absmax: code_kind must be 0 (int8), 1 (uint8) or 2 (f32)");
     if (rows < 0 || num_blocks < 0 || dq_blocks < 0 || blocksize <= 0) return fail(MBNB_ERR_ARG, "dequant_absmax: bad size");
     if (rows == 0 || num_blocks == 0) return MBNB_OK;
@@ -172,6 +195,7 @@ int mbnb_dequant_absmax(const void *codes, int code_kind, int64_t rows, int64_t 
 
 int mbnb_quantize_rowwise(const void *A, int dtype, int64_t rows, int64_t cols, int8_t *out, float *scales,
                           void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "quantize_rowwise: bad dtype");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "quantize_rowwise: negative size");
     if (rows == 0) return MBNB_OK;
@@ -181,6 +205,7 @@ int mbnb_quantize_rowwise(const void *A, int dtype, int64_t rows, int64_t cols, 
 
 int mbnb_dequantize_rowwise(const int8_t *q, const float *scales, int64_t rows, int64_t cols, int out_dtype,
                             void *out, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "dequantize_rowwise: bad dtype");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "dequantize_rowwise: negative size");
     if (rows == 0 || cols == 0) return MBNB_OK;
@@ -190,6 +215,7 @@ int mbnb_dequantize_rowwise(const int8_t *q, const float *scales, int64_t rows, 
 
 int mbnb_double_quant(const void *A, int dtype, int64_t rows, int64_t cols, int8_t *out_col, int8_t *out_row,
                       float *col_stats, float *row_stats, int col_given, int row_given, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "double_quant: bad dtype");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "double_quant: negative size");
     if (rows == 0 || cols == 0) return MBNB_OK;
@@ -201,6 +227,7 @@ int mbnb_double_quant(const void *A, int dtype, int64_t rows, int64_t cols, int8
 int mbnb_matmul_4bit(const void *A, int64_t M, int64_t K, const uint8_t *packed, const mbnb_absmax *absmax, int64_t N,
                      int64_t K_weight, int blocksize, int quant_type, int w_dtype, const void *bias, int out_dtype,
                      void *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (flags & ~MBNB_MATMUL_FUSED_ONLY) return fail(MBNB_ERR_ARG, "matmul_4bit: unknown flags 0x%x", flags);
     if (!dtype_ok(w_dtype) || !dtype_ok(out_dtype) || !qt_ok(quant_type))
         return fail(MBNB_ERR_ARG, "matmul_4bit: bad dtype/quant_type");
@@ -252,6 +279,7 @@ int64_t mbnb_linear_int8_workspace_bytes(int64_t M, int64_t N, int64_t K, int fl
 
 int mbnb_gemm_dense(const void *A, const void *W, int dtype, const void *bias, int out_dtype, void *out, int64_t M, int64_t N,
                     int64_t K, int64_t ldw, void *workspace, int64_t workspace_bytes, int slices, void *stream) {
+    begin_call();
     // slices: bits 0-7 the K slices; bits 8-15 the diagnostic tile code (0 the library's choice; 1 256 x 128 tiles, 2 256 x 256 tiles in uniform columns,
     // 3 128 x 128 tiles, 5 / 6 / 7 a forced column-balanced grid of 32 (code + 1) | 32 code wide columns, bits 16-31 how many of the wider)
     const int tile_m = ((slices >> 8) & 0xFF) * 128, forced_cols_a = (slices >> 16) & 0xFFFF;
@@ -292,6 +320,7 @@ int64_t mbnb_matmul_int8_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 
 int mbnb_matmul_int8(const int8_t *A, const int8_t *B, const float *A_scales, const float *B_scales, int64_t M,
                      int64_t N, int64_t K, int out_dtype, void *out, void *workspace, int64_t workspace_bytes, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "matmul_int8: bad dtype");
     if (M < 0 || N < 0 || K < 0) return fail(MBNB_ERR_ARG, "matmul_int8: negative size");
     if (M == 0 || N == 0) return MBNB_OK;
@@ -303,6 +332,7 @@ int mbnb_matmul_int8(const int8_t *A, const int8_t *B, const float *A_scales, co
 
 int mbnb_linear_int8(const void *X, int dtype, int64_t M, int64_t K, const int8_t *W, const float *W_scales, int64_t N,
                      const void *bias, void *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (flags & ~MBNB_MATMUL_FUSED_ONLY) return fail(MBNB_ERR_ARG, "linear_int8: unknown flags 0x%x", flags);
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "linear_int8: bad dtype");
     if (M < 0 || N < 0 || K < 0 || workspace_bytes < 0) return fail(MBNB_ERR_ARG, "linear_int8: negative size");
@@ -315,6 +345,7 @@ int mbnb_linear_int8(const void *X, int dtype, int64_t M, int64_t K, const int8_
 int mbnb_embedding_4bit(const int64_t *indices, int64_t n_indices, const uint8_t *weight_packed, const float *weight_absmax,
                         int64_t num_embeddings, int64_t embedding_dim, int blocksize, int quant_type, int has_padding,
                         int64_t padding_idx, int out_dtype, void *out, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "embedding_4bit: bad dtype");
     if (!qt_ok(quant_type)) return fail(MBNB_ERR_ARG, "embedding_4bit: bad quant_type");
     if (n_indices < 0 || num_embeddings <= 0 || embedding_dim <= 0 || blocksize <= 0)
@@ -330,6 +361,7 @@ int mbnb_embedding_4bit(const int64_t *indices, int64_t n_indices, const uint8_t
 int mbnb_embedding_8bit(const int64_t *indices, int64_t n_indices, const int8_t *weight_int8, const float *weight_scales,
                         int64_t num_embeddings, int64_t embedding_dim, int has_padding, int64_t padding_idx, int out_dtype,
                         void *out, void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "embedding_8bit: bad dtype");
     if (n_indices < 0 || num_embeddings <= 0 || embedding_dim <= 0) return fail(MBNB_ERR_ARG, "embedding_8bit: bad size");
     if (n_indices == 0) return MBNB_OK;
@@ -346,6 +378,7 @@ int64_t mbnb_outlier_linear_workspace_bytes(int64_t M, int64_t K, int64_t n_outl
 int mbnb_outlier_linear(const void *X, int dtype, int64_t M, int64_t K, const int8_t *W, const float *W_scales, int64_t N,
                         const int64_t *outlier_idx, int64_t n_outliers, const void *outlier_w, const void *bias, void *out,
                         void *workspace, int64_t workspace_bytes, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "outlier_linear: bad dtype");
     if (M < 0 || N < 0 || K <= 0 || n_outliers < 0) return fail(MBNB_ERR_ARG, "outlier_linear: bad size");
     if (M == 0 || N == 0) return MBNB_OK;
@@ -359,6 +392,7 @@ int mbnb_outlier_linear(const void *X, int dtype, int64_t M, int64_t K, const in
 }
 
 int mbnb_quantize_fp8_e4m3(const void *A, int dtype, int64_t rows, int64_t cols, uint8_t *out, float *scales, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "quantize_fp8_e4m3: bad dtype");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "quantize_fp8_e4m3: negative size");
     if (rows == 0 || cols == 0) return MBNB_OK;
@@ -368,6 +402,7 @@ int mbnb_quantize_fp8_e4m3(const void *A, int dtype, int64_t rows, int64_t cols,
 
 int mbnb_dequantize_fp8_e4m3(const uint8_t *q, const float *scales, int64_t rows, int64_t cols, int out_dtype, void *out,
                              void *stream) {
+    begin_call();
     if (!dtype_ok(out_dtype)) return fail(MBNB_ERR_ARG, "dequantize_fp8_e4m3: bad dtype");
     if (rows < 0 || cols < 0) return fail(MBNB_ERR_ARG, "dequantize_fp8_e4m3: negative size");
     if (rows == 0 || cols == 0) return MBNB_OK;
@@ -377,6 +412,7 @@ int mbnb_dequantize_fp8_e4m3(const uint8_t *q, const float *scales, int64_t rows
 
 int mbnb_linear_fp8(const void *X, int dtype, int64_t M, int64_t K, const uint8_t *W, const float *W_scales, int64_t N,
                     const void *bias, void *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (flags & ~MBNB_MATMUL_FUSED_ONLY) return fail(MBNB_ERR_ARG, "linear_fp8: unknown flags 0x%x", flags);
     if (!dtype_ok(dtype)) return fail(MBNB_ERR_ARG, "linear_fp8: bad dtype");
     if (M < 0 || N < 0 || K < 0 || workspace_bytes < 0) return fail(MBNB_ERR_ARG, "linear_fp8: negative size");
@@ -394,6 +430,7 @@ int64_t mbnb_linear_grad_input_workspace_bytes(int64_t M, int64_t N, int64_t K, 
 int mbnb_linear_grad_input(const void *dY, int64_t M, int64_t N, int w_format, const void *W, const mbnb_absmax *absmax, const float *scales,
                            int64_t K, int64_t K_weight, int blocksize, int w_dtype, int out_dtype, void *dX, void *workspace,
                            int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (flags & ~MBNB_GRAD_TRANSPOSE_ONLY) return fail(MBNB_ERR_ARG, "linear_grad_input: unknown flags 0x%x", flags);
     const bool transpose_only = (flags & MBNB_GRAD_TRANSPOSE_ONLY) != 0;
     if (!wfmt_ok(w_format)) return fail(MBNB_ERR_ARG, "linear_grad_input: bad w_format %d", w_format);

@@ -248,6 +248,9 @@ __device__ __forceinline__ void store_out16(u32x4 *dst, u32x4 v) {
 }
 void set_error(const char *fmt, ...);
 void set_kernel_name(const char *name);
+// The variant of the call's GEMM launch: the kernel and its non-type template arguments or runtime branch ("gemv_lean ku5/KU6",
+// "small MF8 NF2 S16 x3", "dense_nb 8/7"), set where a launcher picks it.  Composite paths overwrite the name, never the variant.
+void set_kernel_variant(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 int check_launch(const char *what);
 // Raise a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) ONCE per (device, kernel): the
 // attribute belongs to the current device's copy of the function, so the record is kept per device; later calls are

@@ -150,6 +150,7 @@ static int launch_gemm_dense_fm(const T *x, const T *wd, const T *bias, void *ou
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), GD_LDS, "matmul_4bit(dense)")) return rc;
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), GD_LDS, st, x, wd, bias, out, out_dtype, static_cast<float *>(nullptr),
                            M, N, K, ldw, K, static_cast<const float *>(nullptr), static_cast<const float *>(nullptr), OutlierEpilogue{});
+        set_kernel_variant("%s", FM == 8 ? "dense 256x256" : "dense 256x128");
         set_kernel_name(FM == 8 ? "dense 256x256" : "dense 256x128");
         return check_launch("matmul_4bit(dense)");
     }
@@ -168,6 +169,7 @@ static int launch_gemm_dense_fm(const T *x, const T *wd, const T *bias, void *ou
         hipLaunchKernelGGL((k_splitk_reduce_rm<T, f16_t>), dim3(blocks), dim3(256), 0, st, partial, (int)used, bias, static_cast<f16_t *>(out), M, N);
     else
         hipLaunchKernelGGL((k_splitk_reduce_rm<T, bf16_t>), dim3(blocks), dim3(256), 0, st, partial, (int)used, bias, static_cast<bf16_t *>(out), M, N);
+    set_kernel_variant("%s x%d", FM == 8 ? "dense 256x256" : "dense 256x128", (int)used);
     set_kernel_name(FM == 8 ? "dense 256x256_splitk" : "dense 256x128_splitk");
     return check_launch("matmul_4bit(dense split-K reduce)");
 }
@@ -184,6 +186,7 @@ static int launch_gemm_dense_nb(const T *x, const T *wd, const T *bias, void *ou
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), GD_LDS, "matmul_4bit(dense nb)")) return rc;           \
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), GD_LDS, st, x, wd, bias, out, out_dtype, M, N, K, ldw, tiles_n, \
                            pl.cols_a);                                                                                           \
+        set_kernel_variant("dense_nb %d/%d", FNA, FNB);                                                                          \
     } while (0)
     if (pl.fna == 8) MBNB_NB(8, 7);
     else if (pl.fna == 7) MBNB_NB(7, 6);
@@ -204,6 +207,7 @@ static int launch_gemm_dense128(const T *x, const T *wd, const T *bias, void *ou
     auto kern = k_gemm_dense128<T>;
     if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), G128_LDS, "matmul_4bit(dense128)")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), G128_LDS, st, x, wd, bias, out, out_dtype, M, N, K, ldw);
+    set_kernel_variant("dense 128x128");
     set_kernel_name("dense 128x128");
     return check_launch("matmul_4bit(dense128)");
 }
@@ -301,6 +305,7 @@ int launch_gemm_i8_dense(const int8_t *A, const int8_t *Bt, const float *sA, con
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), GD_LDS, st, reinterpret_cast<const bf16_t *>(A),
                            reinterpret_cast<const bf16_t *>(Bt), static_cast<const bf16_t *>(nullptr), out, out_dtype,
                            static_cast<float *>(nullptr), M, N, K / 2, K / 2, K / 2, sA, sB, *ep);
+        set_kernel_variant("i8_dense OUTL%d NCH%d", out_dtype == MBNB_F16 ? 1 : 2, two ? 2 : 1);
         return check_launch("matmul_int8(dense+outliers)");
     }
     auto kern = k_gemm_dense<bf16_t, false, 8, true>;
@@ -308,6 +313,7 @@ int launch_gemm_i8_dense(const int8_t *A, const int8_t *Bt, const float *sA, con
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), GD_LDS, st, reinterpret_cast<const bf16_t *>(A),
                        reinterpret_cast<const bf16_t *>(Bt), static_cast<const bf16_t *>(nullptr), out, out_dtype,
                        static_cast<float *>(nullptr), M, N, K / 2, K / 2, K / 2, sA, sB, OutlierEpilogue{});
+    set_kernel_variant("i8_dense");
     return check_launch("matmul_int8(dense)");
 }
 

@@ -203,6 +203,8 @@ int matmul_4bit_f32_path(const void *A, int64_t M, int64_t K, const uint8_t *pac
     const float *x = static_cast<const float *>(A), *b = static_cast<const float *>(bias);
     const int rc = p.bt == 128 ? launch_gemm_f32<128>(x, wd, b, out, out_dtype, partial, M, N, K, K_weight, p.slices, p.kps, st)
                                : launch_gemm_f32<64>(x, wd, b, out, out_dtype, partial, M, N, K, K_weight, p.slices, p.kps, st);
+    if (p.bt == 128) set_kernel_variant("f32 128");
+    else set_kernel_variant("f32 64 x%d", (int)p.slices);
     set_kernel_name(p.slices > 1 ? "dequant+dense_f32_splitk" : "dequant+dense_f32");
     return rc;
 }

@@ -18,6 +18,7 @@ static int launch_fused4(const T *x, const typename Q4ProducerRT<T, NESTED>::Par
     if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), GF_LDS, "matmul_4bit(fused4)")) return rc;
     const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), GF_LDS, st, x, wp, bias, out, out_dtype, M, N, K);
+    set_kernel_variant("fused4");
     return check_launch("matmul_4bit(fused4)");
 }
 

@@ -48,9 +48,11 @@ int launch_gemm_mid(const T *x, const typename Q4ProducerRT<T, NESTED>::Params &
     if (slices <= 1) {
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), MID_LDS, st, x, wp, bias, static_cast<void *>(out), od,
                            static_cast<float *>(nullptr), M, N, K, 1, K);
+        set_kernel_variant("mid");
         set_kernel_name("mfma_mid");
         return check_launch("matmul_4bit(mid)");
     }
+    set_kernel_variant("mid x%d", (int)slices);
     set_kernel_name("mfma_mid_splitk");
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * slices)), dim3(512), MID_LDS, st, x, wp, bias, static_cast<void *>(out), od, ws,
                        M, N, K, (int)slices, kps);

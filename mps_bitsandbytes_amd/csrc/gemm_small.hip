@@ -119,17 +119,19 @@ int launch_gemm_small(const T *x, const uint8_t *packed, const AbsmaxView &am, c
         if (K / 256 > (M > 64 ? 16 : 8)) return MBNB_NOT_APPLICABLE;
         plan = SmallPlan{1, 1, 0.0, M > 64 ? 8 : 4};
     }
-#define MBNB_SMALL(MF, NF) return launch_gemm_small_mf<T, OutT, NESTED, MF, NF>(x, packed, am, bias, out, M, N, K, K_weight, qt, bs_shift, ws, ws_bytes, plan.slices, st)
-    if (M <= 64) {
-        MBNB_SMALL(4, 1);
-    }
-    if (plan.mf == 4)
-        return launch_gemm_small_mf<T, OutT, NESTED, 4, 1, 16>(x, packed, am, bias, out, M, N, K, K_weight, qt, bs_shift, ws, ws_bytes, plan.slices, st);
-    if (plan.nf == 2)
-        return launch_gemm_small_mf<T, OutT, NESTED, 8, 2, 16>(x, packed, am, bias, out, M, N, K, K_weight, qt, bs_shift, ws, ws_bytes, plan.slices, st);
-    if ((K / 256 + plan.slices - 1) / plan.slices > 8)
-        return launch_gemm_small_mf<T, OutT, NESTED, 8, 1, 16>(x, packed, am, bias, out, M, N, K, K_weight, qt, bs_shift, ws, ws_bytes, plan.slices, st);
-    MBNB_SMALL(8, 1);
+    // the slices that run (no empty slice: launch_gemm_small_mf), for the variant
+    const int64_t per = (K / 256 + plan.slices - 1) / plan.slices, used = (K / 256 + per - 1) / per;
+#define MBNB_SMALL(MF, NF, MAXS)                                                                                                             \
+    do {                                                                                                                                     \
+        set_kernel_variant("small MF%d NF%d S%d x%d", MF, NF, MAXS, (int)used);                                                              \
+        return launch_gemm_small_mf<T, OutT, NESTED, MF, NF, MAXS>(x, packed, am, bias, out, M, N, K, K_weight, qt, bs_shift, ws, ws_bytes, \
+                                                                   plan.slices, st);                                                         \
+    } while (0)
+    if (M <= 64) MBNB_SMALL(4, 1, 0);
+    if (plan.mf == 4) MBNB_SMALL(4, 1, 16);
+    if (plan.nf == 2) MBNB_SMALL(8, 2, 16);
+    if (per > 8) MBNB_SMALL(8, 1, 16);
+    MBNB_SMALL(8, 1, 0);
 #undef MBNB_SMALL
 }
 

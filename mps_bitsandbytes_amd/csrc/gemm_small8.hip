@@ -26,6 +26,7 @@ int launch_gemm_small8(const T *x, const uint8_t *W, const float *scales, const 
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), lds, "linear_int8(small)")) return rc;             \
         const dim3 grid((unsigned)((N + 63) / 64), (unsigned)used, (unsigned)((M + 16 * MF - 1) / (16 * MF)));               \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, x, W, scales, bias, out, used > 1 ? ws : nullptr, M, N, K, kps);  \
+        set_kernel_variant("small8 MF%d x%d", MF, (int)used);                                                                \
     } while (0)
     if (M <= 64) MBNB_S8(4);
     else MBNB_S8(8);

@@ -611,16 +611,18 @@ __global__ __launch_bounds__(256) void k_linear_i8_generic(const T *__restrict__
                                                           T *__restrict__ out, int64_t M, int64_t N, int64_t K) {
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t m = blockIdx.y;
     if (n >= N) return;
     const float s = w8_row_scale<WF>(scales[n]);
-    float acc = 0.0f;
-    for (int64_t k = lane; k < K; k += 64) {
-        const float w = to_f32(from_f32<T>(w8_decode<WF>((uint32_t)(uint8_t)W[n * K + k]) * s));
-        acc = fmaf(to_f32(X[m * K + k]), w, acc);
+    // grid.y is capped at 65535 (launch_linear_int8): a workgroup walks the rows blockIdx.y, blockIdx.y + gridDim.y, ...
+    for (int64_t m = blockIdx.y; m < M; m += gridDim.y) {
+        float acc = 0.0f;
+        for (int64_t k = lane; k < K; k += 64) {
+            const float w = to_f32(from_f32<T>(w8_decode<WF>((uint32_t)(uint8_t)W[n * K + k]) * s));
+            acc = fmaf(to_f32(X[m * K + k]), w, acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) out[m * N + n] = from_f32<T>(acc + (bias ? to_f32(bias[n]) : 0.0f));
     }
-    acc = wave_sum(acc);
-    if (lane == 0) out[m * N + n] = from_f32<T>(acc + (bias ? to_f32(bias[n]) : 0.0f));
 }
 
 // ------------------------------------------------------------------ skinny W8A16 (1 <= M <= 64)
@@ -723,6 +725,7 @@ static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t 
     do {                                                                                                            \
         constexpr int lds = 16 * MT * 1024;                                                                         \
         hipLaunchKernelGGL((k_skinny8<T, MT, WF>), dim3(grid), dim3(1024), lds, st, x, W, scales, b, o, M, N, K);       \
+        set_kernel_variant("skinny8 MT%d", MT);                                                                     \
     } while (0)
             if (M <= 16) MBNB_SKINNY8(1);
             else if (M <= 32) MBNB_SKINNY8(2);
@@ -744,6 +747,7 @@ static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t 
             constexpr int ldsw = gemm256w_lds_bytes();
             if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kw), ldsw, "linear_int8(mfma256w)")) return rc;
             hipLaunchKernelGGL(kw, dim3((unsigned)tiles), dim3(512), ldsw, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
+            set_kernel_variant("gemm256w");
             set_kernel_name(WF == W8_INT8 ? "w8a16_mfma256" : "fp8a16_mfma256");
             return check_launch("linear_int8(mfma256w)");
         }
@@ -764,16 +768,20 @@ static int launch_linear_int8(const void *X, int64_t M, int64_t K, const int8_t 
                 if (rc) return rc;
                 hipLaunchKernelGGL((k_splitk_reduce<T, T>), dim3((unsigned)(tiles * 16)), dim3(256), 0, st, ws, (int)slices, b, o,
                                    M, N, (M + BM - 1) / BM, tiles);
+                set_kernel_variant("decode128 x%d", (int)slices);
                 set_kernel_name(WF == W8_INT8 ? "w8a16_mfma128_splitk" : "fp8a16_mfma128_splitk");
                 return check_launch("linear_int8(split-K reduce)");
             }
             hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, x, wp, b, o, M, N, K, static_cast<float *>(nullptr), (int64_t)0);
+            set_kernel_variant("decode128");
             set_kernel_name(WF == W8_INT8 ? "w8a16_mfma128" : "fp8a16_mfma128");
             return check_launch("linear_int8(mfma)");
         }
     }
-    hipLaunchKernelGGL((k_linear_i8_generic<T, WF>), dim3((unsigned)((N + 3) / 4), (unsigned)M), dim3(256), 0, st, x, W, scales,
-                       b, o, M, N, K);
+    // one row per grid.y, which holds 65535 at the most: beyond that the kernel walks the remaining rows
+    hipLaunchKernelGGL((k_linear_i8_generic<T, WF>), dim3((unsigned)((N + 3) / 4), (unsigned)(M < 65535 ? M : 65535)), dim3(256), 0, st, x, W,
+                       scales, b, o, M, N, K);
+    set_kernel_variant("linear8_generic");
     set_kernel_name(WF == W8_INT8 ? "w8a16_generic" : "fp8a16_generic");
     return check_launch("linear_int8(generic)");
 }

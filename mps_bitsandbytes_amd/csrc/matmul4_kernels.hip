@@ -37,62 +37,64 @@ __global__ __launch_bounds__(256) void k_matmul4_generic(const T *__restrict__ X
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t m0 = (int64_t)blockIdx.y * MT;
     if (n >= N) return;
     const int64_t nblk = K_weight >> bs_shift;
     const bool wfast = flags & 1, xvec = flags & 2;
-    float acc[MT];
+    // grid.y is capped at 65535 (launch_matmul4): a workgroup walks the row groups blockIdx.y, blockIdx.y + gridDim.y, ...
+    for (int64_t m0 = (int64_t)blockIdx.y * MT; m0 < M; m0 += (int64_t)gridDim.y * MT) {
+        float acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; i++) acc[i] = 0.0f;
-    for (int64_t k0 = (int64_t)lane * 8; k0 < K; k0 += 512) {
-        float w[8];
-        if (wfast) {
-            const int64_t flat = n * K_weight + k0;
-            const uint32_t pk = *reinterpret_cast<const uint32_t *>(packed + (flat >> 1));
-            const float a = load_absmax<NESTED>(am, n * nblk + (k0 >> bs_shift));
+        for (int i = 0; i < MT; i++) acc[i] = 0.0f;
+        for (int64_t k0 = (int64_t)lane * 8; k0 < K; k0 += 512) {
+            float w[8];
+            if (wfast) {
+                const int64_t flat = n * K_weight + k0;
+                const uint32_t pk = *reinterpret_cast<const uint32_t *>(packed + (flat >> 1));
+                const float a = load_absmax<NESTED>(am, n * nblk + (k0 >> bs_shift));
 #pragma unroll
-            for (int j = 0; j < 8; j++)
-                w[j] = (k0 + j < K) ? to_f32(from_f32<T>(lut[(pk >> (4 * j)) & 15] * a)) : 0.0f;   // weight rounded to its dtype (functional.py:382)
-        } else {
+                for (int j = 0; j < 8; j++)
+                    w[j] = (k0 + j < K) ? to_f32(from_f32<T>(lut[(pk >> (4 * j)) & 15] * a)) : 0.0f;   // weight rounded to its dtype (functional.py:382)
+            } else {
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int64_t k = k0 + j;
-                if (k < K) {
-                    const int64_t flat = n * K_weight + k;
-                    const uint8_t b = packed[flat >> 1];
-                    const int idx = (flat & 1) ? (b >> 4) : (b & 15);
-                    const float v = lut[idx] * load_absmax<NESTED>(am, n * nblk + (k >> bs_shift));
-                    w[j] = to_f32(from_f32<T>(v));
-                } else w[j] = 0.0f;
+                for (int j = 0; j < 8; j++) {
+                    const int64_t k = k0 + j;
+                    if (k < K) {
+                        const int64_t flat = n * K_weight + k;
+                        const uint8_t b = packed[flat >> 1];
+                        const int idx = (flat & 1) ? (b >> 4) : (b & 15);
+                        const float v = lut[idx] * load_absmax<NESTED>(am, n * nblk + (k >> bs_shift));
+                        w[j] = to_f32(from_f32<T>(v));
+                    } else w[j] = 0.0f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < MT; i++) {
+                const int64_t m = m0 + i;
+                if (m < M) {
+                    if (xvec && k0 + 8 <= K) {
+                        __attribute__((aligned(16))) T xv[8];
+                        constexpr int NV = (int)sizeof(T) * 8 / 16;
+#pragma unroll
+                        for (int v = 0; v < NV; v++)
+                            reinterpret_cast<u32x4 *>(xv)[v] = reinterpret_cast<const u32x4 *>(X + m * K + k0)[v];
+#pragma unroll
+                        for (int j = 0; j < 8; j++) acc[i] = fmaf(to_f32(xv[j]), w[j], acc[i]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; j++)
+                            if (k0 + j < K) acc[i] = fmaf(to_f32(X[m * K + k0 + j]), w[j], acc[i]);
+                    }
+                }
             }
         }
 #pragma unroll
         for (int i = 0; i < MT; i++) {
+            const float s = wave_sum(acc[i]);
             const int64_t m = m0 + i;
-            if (m < M) {
-                if (xvec && k0 + 8 <= K) {
-                    __attribute__((aligned(16))) T xv[8];
-                    constexpr int NV = (int)sizeof(T) * 8 / 16;
-#pragma unroll
-                    for (int v = 0; v < NV; v++)
-                        reinterpret_cast<u32x4 *>(xv)[v] = reinterpret_cast<const u32x4 *>(X + m * K + k0)[v];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) acc[i] = fmaf(to_f32(xv[j]), w[j], acc[i]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; j++)
-                        if (k0 + j < K) acc[i] = fmaf(to_f32(X[m * K + k0 + j]), w[j], acc[i]);
-                }
+            if (lane == 0 && m < M) {
+                float v = s + (bias ? to_f32(bias[n]) : 0.0f);
+                out[m * N + n] = from_f32<OutT>(to_f32(from_f32<T>(v)));
             }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < MT; i++) {
-        const float s = wave_sum(acc[i]);
-        const int64_t m = m0 + i;
-        if (lane == 0 && m < M) {
-            float v = s + (bias ? to_f32(bias[n]) : 0.0f);
-            out[m * N + n] = from_f32<OutT>(to_f32(from_f32<T>(v)));
         }
     }
 }
@@ -277,6 +279,7 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
         else                                                                                                        \
             hipLaunchKernelGGL((k_gemv4<T, OutT, QT, NESTED, MT, NR, KU, false>), grid, dim3(256), 0, st, x, packed, \
                                am, b, o, M, N, K, K_weight, sh);                                                    \
+        set_kernel_variant("gemv MT%d NR%d KU%d %s", MT, NR, KU, xlds ? "lds" : "regs");                            \
     } while (0)
             // M = 1, blocksize 64, K % 64 == 0 up to 16384 (round 3): k_gemv4_lean -- the same arithmetic with the per-wave fixed cost
             // cut (480 instead of 627 instructions per wave: buffer descriptors instead of 64-bit address VALU, table from
@@ -287,7 +290,11 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
                 if (M == 1 && blocksize == 64 && K_weight == K && K % 64 == 0 && K >= 1024 && ku <= 8 && N * (K / 2) < ((int64_t)1 << 40) &&
                     (!NESTED || (am.bs2 > 0 && (am.bs2 & (am.bs2 - 1)) == 0 && (reinterpret_cast<uintptr_t>(am.i8) & 3) == 0 && (K / 64) % 4 == 0))) {
                     const dim3 grid((unsigned)((N + 3) / 4));
-#define MBNB_LEAN(KU) hipLaunchKernelGGL((k_gemv4_lean<T, OutT, QT, NESTED, KU>), grid, dim3(256), (size_t)KU * 4096, st, x, packed, am, b, o, N, K)
+#define MBNB_LEAN(KU)                                                                                                                      \
+    do {                                                                                                                               \
+        hipLaunchKernelGGL((k_gemv4_lean<T, OutT, QT, NESTED, KU>), grid, dim3(256), (size_t)KU * 4096, st, x, packed, am, b, o, N, K); \
+        set_kernel_variant("gemv_lean ku%d/KU%d", (int)ku, KU);                                                                        \
+    } while (0)
                     if (ku == 1) MBNB_LEAN(1);
                     else if (ku == 2) MBNB_LEAN(2);
                     else if (ku == 3) MBNB_LEAN(3);
@@ -325,6 +332,7 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
         }                                                                                                            \
         hipLaunchKernelGGL(kern, dim3((unsigned)((N + 16 * NR - 1) / (16 * NR))), dim3(1024), lds, st, x, packed, am, b, o, M, N, \
                            K, K_weight, sh);                                                                         \
+        set_kernel_variant("skinny MT%d NR%d", MT, NR);                                                              \
     } while (0)
             // one 16-row group per workgroup (N / 16 workgroups): measured faster than two at every shape tried
             // (tools/m_sweep2.py), the extra activation traffic notwithstanding
@@ -375,12 +383,14 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
                 constexpr int lds = gemm256p_lds_bytes<NESTED>();
                 if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), lds, "matmul_4bit(mfma256)")) return rc;
                 hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), lds, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
+                set_kernel_variant(am4 ? "gemm256p am4" : "gemm256p");
                 set_kernel_name("mfma256");
                 return check_launch("matmul_4bit(mfma256)");
             }
             auto kern = k_gemm256<T, P>;
             if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(kern), G256_LDS, "matmul_4bit(mfma256)")) return rc;
             hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), G256_LDS, st, x, wp, b, static_cast<void *>(o), od, M, N, K);
+            set_kernel_variant("gemm256");
             set_kernel_name("mfma256");
             return check_launch("matmul_4bit(mfma256)");
         }
@@ -400,10 +410,12 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
                 if (rc) return rc;
                 hipLaunchKernelGGL((k_splitk_reduce<T, OutT>), dim3((unsigned)(tiles * 16)), dim3(256), 0, st, ws, (int)slices,
                                    b, o, M, N, (M + BM - 1) / BM, tiles);
+                set_kernel_variant("decode128 x%d", (int)slices);
                 set_kernel_name("mfma128_splitk");
                 return check_launch("matmul_4bit(split-K reduce)");
             }
             hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, x, wp, b, o, M, N, K, static_cast<float *>(nullptr), (int64_t)0);
+            set_kernel_variant("decode128");
             set_kernel_name("mfma128");
             return check_launch("matmul_4bit(mfma128)");
         }
@@ -413,15 +425,21 @@ static int launch_matmul4(const void *A, int64_t M, int64_t K, const uint8_t *pa
         const int bs_shift = ilog2(blocksize);
         const int flags = ((K_weight % 8 == 0 && blocksize >= 8 && (reinterpret_cast<uintptr_t>(packed) & 3) == 0) ? 1 : 0) |
                           (((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (K * (int64_t)sizeof(T)) % 16 == 0) ? 2 : 0);
-        if (M == 1)
+        if (M == 1) {
             hipLaunchKernelGGL((k_matmul4_generic<T, OutT, QT, NESTED, 1>), dim3(gx, 1), dim3(256), 0, st, x,
                                packed, am, b, o, M, N, K, K_weight, bs_shift, flags);
-        else if (M <= 4)   // the packed weight once for all rows
+            set_kernel_variant("generic ROWS1 flags%d", flags);
+        } else if (M <= 4) {   // the packed weight once for all rows
             hipLaunchKernelGGL((k_matmul4_generic<T, OutT, QT, NESTED, 4>), dim3(gx, 1), dim3(256), 0, st, x,
                                packed, am, b, o, M, N, K, K_weight, bs_shift, flags);
-        else
-            hipLaunchKernelGGL((k_matmul4_generic<T, OutT, QT, NESTED, 8>), dim3(gx, (unsigned)((M + 7) / 8)),
+            set_kernel_variant("generic ROWS4 flags%d", flags);
+        } else {
+            // groups of 8 rows in grid.y, which holds 65535 at the most: beyond that the kernel walks the remaining groups
+            const int64_t gy = (M + 7) / 8;
+            hipLaunchKernelGGL((k_matmul4_generic<T, OutT, QT, NESTED, 8>), dim3(gx, (unsigned)(gy < 65535 ? gy : 65535)),
                                dim3(256), 0, st, x, packed, am, b, o, M, N, K, K_weight, bs_shift, flags);
+            set_kernel_variant("generic ROWS8 flags%d", flags);
+        }
         set_kernel_name("generic");
         return check_launch("matmul_4bit(generic)");
     }

@@ -299,34 +299,43 @@ __global__ __launch_bounds__(256) void k_outlier_add(const T *__restrict__ X, in
     constexpr int RM = 16, CN = 2, CH = 16;
     __shared__ __attribute__((aligned(16))) float xs[RM][CH];
     const int64_t n0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * CN;
-    const int64_t m0 = (int64_t)blockIdx.y * RM;
-    float acc[RM][CN];
+    // grid.y is capped at 65535 (launch_outlier_linear): a workgroup walks the row groups blockIdx.y, blockIdx.y + gridDim.y, ... --
+    // all of its threads together, for the barriers of the gather
+    for (int64_t m0 = (int64_t)blockIdx.y * RM; m0 < M; m0 += (int64_t)gridDim.y * RM) {
+        float acc[RM][CN];
 #pragma unroll
-    for (int i = 0; i < RM; i++)
+        for (int i = 0; i < RM; i++)
 #pragma unroll
-        for (int c = 0; c < CN; c++) acc[i][c] = 0.0f;
-    for (int64_t j0 = 0; j0 < n_out; j0 += CH) {
-        __syncthreads();
-        {
-            const int i = threadIdx.x / CH, j = threadIdx.x % CH;   // 256 threads = RM x CH values
-            const int64_t m = m0 + i;
-            xs[i][j] = (m < M && j0 + j < n_out) ? to_f32(X[m * K + oidx[j0 + j]]) : 0.0f;
-        }
-        __syncthreads();
-        float w[CN][CH];
-        if constexpr (sizeof(T) == 2) {
-            if (ow_vec && n0 + CN <= N && j0 + CH <= n_out) {   // 2 x 16-byte loads per column
+            for (int c = 0; c < CN; c++) acc[i][c] = 0.0f;
+        for (int64_t j0 = 0; j0 < n_out; j0 += CH) {
+            __syncthreads();
+            {
+                const int i = threadIdx.x / CH, j = threadIdx.x % CH;   // 256 threads = RM x CH values
+                const int64_t m = m0 + i;
+                xs[i][j] = (m < M && j0 + j < n_out) ? to_f32(X[m * K + oidx[j0 + j]]) : 0.0f;
+            }
+            __syncthreads();
+            float w[CN][CH];
+            if constexpr (sizeof(T) == 2) {
+                if (ow_vec && n0 + CN <= N && j0 + CH <= n_out) {   // 2 x 16-byte loads per column
 #pragma unroll
-                for (int c = 0; c < CN; c++)
+                    for (int c = 0; c < CN; c++)
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const u32x4 v = *reinterpret_cast<const u32x4 *>(ow + (n0 + c) * n_out + j0 + 8 * h);
+                        for (int h = 0; h < 2; h++) {
+                            const u32x4 v = *reinterpret_cast<const u32x4 *>(ow + (n0 + c) * n_out + j0 + 8 * h);
 #pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            w[c][8 * h + 2 * e] = unpack_lo<T>(v[e]);
-                            w[c][8 * h + 2 * e + 1] = unpack_hi<T>(v[e]);
+                            for (int e = 0; e < 4; e++) {
+                                w[c][8 * h + 2 * e] = unpack_lo<T>(v[e]);
+                                w[c][8 * h + 2 * e + 1] = unpack_hi<T>(v[e]);
+                            }
                         }
-                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CN; c++)
+#pragma unroll
+                        for (int j = 0; j < CH; j++)
+                            w[c][j] = (n0 + c < N && j0 + j < n_out) ? to_f32(ow[(n0 + c) * n_out + j0 + j]) : 0.0f;
+                }
             } else {
 #pragma unroll
                 for (int c = 0; c < CN; c++)
@@ -334,56 +343,50 @@ __global__ __launch_bounds__(256) void k_outlier_add(const T *__restrict__ X, in
                     for (int j = 0; j < CH; j++)
                         w[c][j] = (n0 + c < N && j0 + j < n_out) ? to_f32(ow[(n0 + c) * n_out + j0 + j]) : 0.0f;
             }
-        } else {
 #pragma unroll
-            for (int c = 0; c < CN; c++)
+            for (int i = 0; i < RM; i++)
 #pragma unroll
-                for (int j = 0; j < CH; j++)
-                    w[c][j] = (n0 + c < N && j0 + j < n_out) ? to_f32(ow[(n0 + c) * n_out + j0 + j]) : 0.0f;
+                for (int q = 0; q < CH / 4; q++) {
+                    const f32x4 xv = *reinterpret_cast<const f32x4 *>(&xs[i][4 * q]);   // one broadcast ds_read_b128
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+#pragma unroll
+                        for (int c = 0; c < CN; c++) acc[i][c] = fmaf(xv[e], w[c][4 * q + e], acc[i][c]);
+                }
         }
+        if (n0 >= N) continue;
+        float b[CN];
 #pragma unroll
-        for (int i = 0; i < RM; i++)
+        for (int c = 0; c < CN; c++) b[c] = (bias && n0 + c < N) ? to_f32(bias[n0 + c]) : 0.0f;
+        const bool full = vec_ok && n0 + CN <= N;
 #pragma unroll
-            for (int q = 0; q < CH / 4; q++) {
-                const f32x4 xv = *reinterpret_cast<const f32x4 *>(&xs[i][4 * q]);   // one broadcast ds_read_b128
+        for (int i = 0; i < RM; i++) {
+            const int64_t m = m0 + i;
+            if (m >= M) break;
+            T *p = out + m * N + n0;
+            __attribute__((aligned(8))) T v[CN];
+            if (full) {
+                if constexpr (sizeof(T) == 2) *reinterpret_cast<uint32_t *>(v) = *reinterpret_cast<const uint32_t *>(p);
+                else *reinterpret_cast<u32x2 *>(v) = *reinterpret_cast<const u32x2 *>(p);
+            } else {
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-#pragma unroll
-                    for (int c = 0; c < CN; c++) acc[i][c] = fmaf(xv[e], w[c][4 * q + e], acc[i][c]);
+                for (int c = 0; c < CN; c++) v[c] = (n0 + c < N) ? p[c] : from_f32<T>(0.0f);
             }
-    }
-    if (n0 >= N) return;
-    float b[CN];
 #pragma unroll
-    for (int c = 0; c < CN; c++) b[c] = (bias && n0 + c < N) ? to_f32(bias[n0 + c]) : 0.0f;
-    const bool full = vec_ok && n0 + CN <= N;
+            for (int c = 0; c < CN; c++) {
+                float f = to_f32(v[c]);
+                if (n_out > 0) f = to_f32(from_f32<T>(f + to_f32(from_f32<T>(acc[i][c]))));
+                if (bias) f = to_f32(from_f32<T>(f + b[c]));
+                v[c] = from_f32<T>(f);
+            }
+            if (full) {
+                if constexpr (sizeof(T) == 2) *reinterpret_cast<uint32_t *>(p) = *reinterpret_cast<const uint32_t *>(v);
+                else *reinterpret_cast<u32x2 *>(p) = *reinterpret_cast<const u32x2 *>(v);
+            } else {
 #pragma unroll
-    for (int i = 0; i < RM; i++) {
-        const int64_t m = m0 + i;
-        if (m >= M) break;
-        T *p = out + m * N + n0;
-        __attribute__((aligned(8))) T v[CN];
-        if (full) {
-            if constexpr (sizeof(T) == 2) *reinterpret_cast<uint32_t *>(v) = *reinterpret_cast<const uint32_t *>(p);
-            else *reinterpret_cast<u32x2 *>(v) = *reinterpret_cast<const u32x2 *>(p);
-        } else {
-#pragma unroll
-            for (int c = 0; c < CN; c++) v[c] = (n0 + c < N) ? p[c] : from_f32<T>(0.0f);
-        }
-#pragma unroll
-        for (int c = 0; c < CN; c++) {
-            float f = to_f32(v[c]);
-            if (n_out > 0) f = to_f32(from_f32<T>(f + to_f32(from_f32<T>(acc[i][c]))));
-            if (bias) f = to_f32(from_f32<T>(f + b[c]));
-            v[c] = from_f32<T>(f);
-        }
-        if (full) {
-            if constexpr (sizeof(T) == 2) *reinterpret_cast<uint32_t *>(p) = *reinterpret_cast<const uint32_t *>(v);
-            else *reinterpret_cast<u32x2 *>(p) = *reinterpret_cast<const u32x2 *>(v);
-        } else {
-#pragma unroll
-            for (int c = 0; c < CN; c++)
-                if (n0 + c < N) p[c] = v[c];
+                for (int c = 0; c < CN; c++)
+                    if (n0 + c < N) p[c] = v[c];
+            }
         }
     }
 }
@@ -434,7 +437,8 @@ static int launch_outlier_linear(const void *X, int64_t M, int64_t K, const int8
     rc = matmul_int8_nt_dispatch(xq, W, xs, w_scales, M, N, K, dtype, out, st, ((n_out == 0 || xo != nullptr) && (n_out > 0 || bias)) ? &ep : nullptr, &fused);
     if (rc) return rc;
     if (!fused && (n_out > 0 || bias)) {
-        dim3 grid((unsigned)((N + 511) / 512), (unsigned)((M + 15) / 16));
+        const int64_t gy = (M + 15) / 16;   // groups of 16 rows; grid.y holds 65535 at the most, the kernel walks the rest
+        dim3 grid((unsigned)((N + 511) / 512), (unsigned)(gy < 65535 ? gy : 65535));
         const bool vec_out = (N % 2 == 0) && ((reinterpret_cast<uintptr_t>(out) & 7) == 0);
         const bool ow_vec = (n_out % 8 == 0) && ((reinterpret_cast<uintptr_t>(ow) & 15) == 0);
         hipLaunchKernelGGL(k_outlier_add<T>, grid, dim3(256), 0, st, static_cast<const T *>(X), M, K, N, oidx, n_out,

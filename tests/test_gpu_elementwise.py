@@ -1,7 +1,8 @@
 """
 Every kernel the library can report, element by element against float64, on poisoned allocations.
 
-The cases are the table of tests/kernel_cases.py.  Each runs through the public API (mbnb_gemm_dense through the C ABI) right
+The cases are the tables of tests/kernel_cases.py (one case at least per kernel name) and tests/gemm_variant_cases.py (one per variant
+behind a name, per dispatch limit and per launch-grid limit; those also hold the variant the launcher reports).  Each runs through the public API (mbnb_gemm_dense through the C ABI) right
 after a one-row embedding lookup whose kernel name is known, so a launch that sets no name shows up as that name instead of
 passing on a stale one; it must dispatch to its named kernel, and every output element must lie within the bound of
 tests/elementwise.py around a float64 product of the operands the op feeds the kernel -- the decoded weight taken from the CPU
@@ -9,6 +10,8 @@ oracle, and the library's own dequantise checked against it bit for bit.  Output
 poisoned torch.empty (tests/poison.py), or are poisoned by hand where a test allocates them.  The largest err / bound ratio
 of every case is printed (run with -s).
 """
+import time
+
 import numpy as np
 import pytest
 import torch
@@ -16,7 +19,7 @@ import torch
 import oracle
 from mps_bitsandbytes_amd import _native, synthetic
 from mps_bitsandbytes_amd import functional as F
-from tests import kernel_cases
+from tests import gemm_variant_cases, kernel_cases
 from tests.elementwise import (UNIT, assert_bound_elementwise, assert_int8_elementwise, assert_linear_elementwise,
                                int8_reference)
 from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name)
@@ -31,6 +34,13 @@ _SENTINEL = {}
 def _poison(t):
     t.reshape(-1).view(torch.uint8).fill_(0xFF)
     return t
+
+
+def _offset(t, n):
+    """t's values in a slice that starts n elements into a larger buffer: an operand off its alignment by n elements."""
+    buf = torch.empty(t.numel() + n, dtype=t.dtype, device=t.device)
+    buf[n:] = t.reshape(-1)
+    return buf[n:].view(t.shape)
 
 
 def _sentinel(kernel):
@@ -48,6 +58,7 @@ def _sentinel(kernel):
         F.embedding_8bit(idx, _SENTINEL["q8"], _SENTINEL["s8"])
         name = "embedding8"
     assert _native.last_kernel() == name
+    assert _native.last_variant() == "", "a call whose launcher sets no variant reports the previous call's"
     return name
 
 
@@ -55,6 +66,9 @@ def _check_name(got, c):
     want = c["kernel"]
     ok = got.startswith(want) if want.endswith(" ") else got == want
     assert ok, f"{kernel_cases.case_id(c)}: dispatched {got!r}, the case is for {want!r}"
+    if "variant" in c:
+        variant = _native.last_variant()
+        assert variant == c["variant"], f"{kernel_cases.case_id(c)}: {got!r} took the variant {variant!r}, the case is for {c['variant']!r}"
 
 
 def _same_bits(a, b):
@@ -90,7 +104,7 @@ def _activation(c, K, dt, seed):
         flat = torch.empty(rows * K + 1, dtype=dt, device=DEV)
         flat[1:] = X.reshape(-1)
         X = flat[1:].view(rows, K)
-        assert X.data_ptr() % 16 == 2
+        assert X.data_ptr() % 16 == X.element_size()
     return X.reshape(*lead, K)
 
 
@@ -102,7 +116,10 @@ def _weight_4bit(c, N, K, dt, seed):
     """(packed, QuantState) on the GPU and the oracle's decoded weight [N, K] (a NaN absmax in one block for bad "w")."""
     qt, bs, cs = c.get("qt", "nf4"), c.get("bs", 64), c.get("cs", False)
     W = synthetic.normal((N, K), dt, seed=seed)
-    op, oa, ost2 = oracle.quantize_4bit(W, bs, qt, cs)
+    op, oa, ost2 = oracle.quantize_4bit(W, bs, qt, cs and "bs2" not in c)
+    if "bs2" in c:                                  # the nested absmax at a second blocksize of the case's choosing
+        oa, am2 = oracle.quantize_blockwise(oa, blocksize=c["bs2"])
+        ost2 = (am2, c["bs2"])
     if "w" in c.get("bad", ""):
         assert not cs
         oa = oa.clone()
@@ -111,9 +128,22 @@ def _weight_4bit(c, N, K, dt, seed):
     st2 = None
     if cs:
         st2 = F.QuantState(absmax=ost2[0].to(DEV), shape=torch.Size([oa.numel()]), blocksize=ost2[1], quant_type="int8", dtype=torch.float32)
-    st = F.QuantState(absmax=oa.to(DEV), shape=torch.Size([N, K]), blocksize=bs, quant_type=qt, dtype=dt, state2=st2)
+    am = oa.to(DEV)
+    st = F.QuantState(absmax=am, shape=torch.Size([N, K]), blocksize=bs, quant_type=qt, dtype=dt, state2=st2)
     packed = op.to(DEV)
     assert _same_bits(F.dequantize_4bit(packed, st), Wd), "dequantize_4bit differs from the oracle's decode"
+    view = c.get("view")
+    if view == "absmax+4":                          # the f32 absmax 4 bytes off 16-byte alignment
+        assert not cs
+        st.absmax = _offset(am, 1)
+        assert st.absmax.data_ptr() % 16 == 4
+    elif view == "codes+1":                         # the nested int8 absmax codes 1 byte off 4-byte alignment
+        assert cs and am.dtype == torch.int8
+        st.absmax = _offset(am, 1)
+        assert st.absmax.data_ptr() % 4 == 1
+    elif view in ("packed+4", "packed+2"):          # the packed nibbles off 16-byte / off 4-byte alignment
+        packed = _offset(packed, int(view[-1]))
+        assert packed.data_ptr() % 16 == int(view[-1])
     return packed, st, Wd
 
 
@@ -132,6 +162,9 @@ def _weight_8bit(c, N, K, dt, seed, fp8):
     qd, sd = q.to(DEV), s.to(DEV)
     mine = (F.dequantize_fp8_e4m3 if fp8 else F.dequantize_rowwise)(qd, sd, dt)
     assert _same_bits(mine, Wd), "the library's dequantise differs from the oracle's"
+    if c.get("view") == "w+1":                      # the weight bytes 1 byte off 16-byte alignment
+        qd = _offset(qd, 1)
+        assert qd.data_ptr() % 16 == 1
     return qd, sd, Wd
 
 
@@ -189,6 +222,10 @@ def _run_matmul_int8(c):
     sb = (synthetic.normal((N,), torch.float32, seed=34).abs() + 0.5).to(DEV)
     if "w" in c.get("bad", ""):
         sb[N // 2] = float("nan")
+    if c.get("view") == "a+1":
+        A = _offset(A, 1)
+    elif c.get("view") == "b+1":
+        B = _offset(B, 1)
     _sentinel(c["kernel"])
     y = F.matmul_int8(A, B, sa, sb, odt)
     kern = _native.last_kernel()
@@ -254,6 +291,9 @@ def _run_outlier(c):
     ow = W[:, oidx].contiguous()
     b = synthetic.normal((N,), dt, seed=63) if c.get("bias") else None
     x = synthetic.normal((M, K), dt, seed=64)
+    if "xexp" in c:                                  # rows over many binades, as _activation scales them
+        lo, hi = c["xexp"]
+        x = (x.double() * torch.exp2(torch.linspace(lo, hi, M).round().double())[:, None]).to(dt)
     _sentinel(c["kernel"])
     y = F.outlier_linear(x.to(DEV), q.to(DEV), s.to(DEV), oidx.to(DEV), ow.to(DEV), None if b is None else b.to(DEV), dt)
     kern = _native.last_kernel()
@@ -292,10 +332,14 @@ def _run_embedding(c):
     return kern, 0.0
 
 
+ALL_CASES = kernel_cases.CASES + gemm_variant_cases.CASES
+
+
 @pytest.mark.parametrize("case", [pytest.param(c, marks=pytest.mark.xfail(strict=True, reason=c["xfail"])) if "xfail" in c else c
-                                  for c in kernel_cases.CASES], ids=[kernel_cases.case_id(c) for c in kernel_cases.CASES])
+                                  for c in ALL_CASES], ids=[kernel_cases.case_id(c) for c in ALL_CASES])
 def test_kernel_case_elementwise(case, monkeypatch, poisoned_alloc):
     op = case["op"]
+    t0 = time.perf_counter()
     if op in ("matmul_4bit", "linear_int8", "matmul_fp8", "linear_dense"):
         kern, ratio = _run_linear(case, monkeypatch)
     elif op == "gemm_dense":
@@ -311,7 +355,9 @@ def test_kernel_case_elementwise(case, monkeypatch, poisoned_alloc):
     else:
         kern, ratio = _run_embedding(case)
     assert poisoned_alloc.poisoned > 0
-    print(f"\nelementwise {kern}: max err / bound {ratio:.3g} ({kernel_cases.case_id(case)})")
+    torch.cuda.synchronize()
+    print(f"\nelementwise {kern} [{_native.last_variant() if op not in ('grad', 'grad_t') else ''}]: max err / bound {ratio:.3g} "
+          f"({kernel_cases.case_id(case)}) {time.perf_counter() - t0:.2f} s")
 
 
 def test_matmul_int8_transpose_path_at_the_offset_limit(poisoned_alloc):
