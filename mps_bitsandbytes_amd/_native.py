@@ -10,16 +10,19 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_int, c_int32, c_int64, c_void_p
 from typing import Optional
 
 import torch
+
+from . import _loader
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmbnb_hip.so")
 
 ABI_VERSION = 2   # include/mbnb_hip.h MBNB_ABI_VERSION
-F16, BF16, F32 = 0, 1, 2
+_PREFIX, _CHECK_PREFIX = "mbnb", "mps_bitsandbytes_amd"
+F16, BF16, F32 = 0, 1, 2        # the element-type codes of all five headers
 NF4, FP4 = 0, 1
 W_INT8_ROWWISE, W_FP8_E4M3, W_DENSE = 2, 3, 4   # the other weight formats of mbnb_linear_grad_input
 GRAD_TRANSPOSE_ONLY = 2                         # its flags word: the transposed dequantise pass alone
@@ -87,38 +90,14 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 def available() -> bool:
     """True when libmbnb_hip.so is present and loads (does not need a GPU)."""
-    try:
-        lib()
-        return True
-    except RuntimeError:
-        return False
+    return _loader.loads(lib)
 
 
 def lib():
     """The loaded library; raises RuntimeError (never falls back) when it cannot be loaded."""
-    global _lib, _load_error
     if _lib is not None:
         return _lib
-    if _load_error is not None:
-        raise RuntimeError(_load_error)
-    if not os.path.exists(LIB_PATH):
-        _load_error = (f"mps_bitsandbytes_amd: native library {LIB_PATH} not found. Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` (or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                       f"There is no Python fallback.")
-        raise RuntimeError(_load_error)
-    try:
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.mbnb_abi_version() != ABI_VERSION:
-            raise OSError(f"ABI version mismatch: library reports {handle.mbnb_abi_version()}, binding expects {ABI_VERSION}")
-    except (OSError, AttributeError) as e:
-        _load_error = f"mps_bitsandbytes_amd: cannot load {LIB_PATH}: {e}"
-        raise RuntimeError(_load_error) from e
-    _lib = handle
-    return _lib
+    return _loader.load(globals())
 
 
 def last_kernel() -> str:
@@ -140,8 +119,7 @@ def last_variant() -> str:
 
 def check(status: int, what: str) -> None:
     if status != 0:
-        msg = lib().mbnb_last_error().decode(errors="replace")
-        raise RuntimeError(f"mps_bitsandbytes_amd.{what} failed (status {status}): {msg}")
+        raise _loader.failed(globals(), status, what)
 
 
 def ptr(t: Optional[torch.Tensor]) -> c_void_p:

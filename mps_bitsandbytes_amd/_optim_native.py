@@ -14,20 +14,22 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _loader
+from ._native import BF16, DTYPE_CODE, F16, F32     # one definition; read from this module too
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmbnb_optim.so")
 
 ABI_VERSION = 1            # include/mbnb_optim.h MBNB_OPTIM_ABI_VERSION
+_PREFIX, _CHECK_PREFIX = "mbnb_optim", "mps_bitsandbytes_amd.optim"
 MAX_TENSORS = 48           # MBNB_OPTIM_MAX_TENSORS: descriptors per call (one kernel launch)
 ADAM, ADAMW, LION, SGD_MOMENTUM, SGD_NESTEROV = 0, 1, 2, 3, 4
-F16, BF16, F32 = 0, 1, 2
-DTYPE_CODE = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 WEIGHT_DECAY = 1           # mbnb_optim_scalars.flags
 FORCE_GENERIC = 1          # mbnb_optim_step flags
 
 
 class Scalars(Structure):
-    """mirror of ``struct mbnb_optim_scalars``"""
+    """mirror of ``struct mbnb_optim_scalars`` and of ``struct mbnb_paged_scalars`` (include/mbnb_paged.h), which has its layout"""
     _fields_ = [("beta1", c_float), ("one_minus_beta1", c_float), ("beta2", c_float), ("one_minus_beta2", c_float),
                 ("eps", c_float), ("weight_decay", c_float), ("decay", c_float), ("neg_lr", c_float),
                 ("flags", c_int32), ("pad_", c_int32)]
@@ -65,43 +67,19 @@ def reset_launch_log() -> None:
 
 
 def available() -> bool:
-    try:
-        lib()
-        return True
-    except RuntimeError:
-        return False
+    return _loader.loads(lib)
 
 
 def lib():
     """The loaded library; raises RuntimeError (never falls back) when it cannot be loaded."""
-    global _lib, _load_error
     if _lib is not None:
         return _lib
-    if _load_error is not None:
-        raise RuntimeError(_load_error)
-    if not os.path.exists(LIB_PATH):
-        _load_error = (f"mps_bitsandbytes_amd.optim: native library {LIB_PATH} not found. Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}`. There is no Python fallback.")
-        raise RuntimeError(_load_error)
-    try:
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.mbnb_optim_abi_version() != ABI_VERSION:
-            raise OSError(f"ABI version mismatch: library reports {handle.mbnb_optim_abi_version()}, binding expects {ABI_VERSION}")
-    except (OSError, AttributeError) as e:
-        _load_error = f"mps_bitsandbytes_amd.optim: cannot load {LIB_PATH}: {e}"
-        raise RuntimeError(_load_error) from e
-    _lib = handle
-    return _lib
+    return _loader.load(globals())
 
 
 def check(status: int, what: str) -> None:
     if status != 0:
-        msg = lib().mbnb_optim_last_error().decode(errors="replace")
-        raise RuntimeError(f"mps_bitsandbytes_amd.optim.{what} failed (status {status}): {msg}")
+        raise _loader.failed(globals(), status, what)
 
 
 def n_blocks(numel: int, block_size: int) -> int:

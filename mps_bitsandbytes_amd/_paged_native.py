@@ -8,29 +8,25 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_void_p
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import _loader
+from ._native import BF16, DTYPE_CODE, F16, F32     # one definition; read from this module too
+from ._optim_native import Scalars          # struct mbnb_paged_scalars: the layout of mbnb_optim_scalars
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmbnb_paged.so")
 
 ABI_VERSION = 1            # include/mbnb_paged.h MBNB_PAGED_ABI_VERSION
+_PREFIX, _CHECK_PREFIX = "mbnb_paged", "mps_bitsandbytes_amd.optim.paged"
 MAX_SEGMENTS = 48          # MBNB_PAGED_MAX_SEGMENTS: segments per call (one kernel launch)
 ADAM, ADAMW, LION = 0, 1, 2
-F16, BF16, F32 = 0, 1, 2
-DTYPE_CODE = {torch.float16: F16, torch.bfloat16: BF16, torch.float32: F32}
 WEIGHT_DECAY = 1           # mbnb_paged_scalars.flags
 FORCE_SCALAR = 1           # mbnb_paged_step flags
-
-
-class Scalars(Structure):
-    """mirror of ``struct mbnb_paged_scalars``"""
-    _fields_ = [("beta1", c_float), ("one_minus_beta1", c_float), ("beta2", c_float), ("one_minus_beta2", c_float),
-                ("eps", c_float), ("weight_decay", c_float), ("decay", c_float), ("neg_lr", c_float),
-                ("flags", c_int32), ("pad_", c_int32)]
 
 
 # the same layout as a numpy record: a whole table is built in one np.array call
@@ -63,43 +59,19 @@ def reset_launch_log() -> None:
 
 
 def available() -> bool:
-    try:
-        lib()
-        return True
-    except RuntimeError:
-        return False
+    return _loader.loads(lib)
 
 
 def lib():
     """The loaded library; raises RuntimeError (never falls back) when it cannot be loaded."""
-    global _lib, _load_error
     if _lib is not None:
         return _lib
-    if _load_error is not None:
-        raise RuntimeError(_load_error)
-    if not os.path.exists(LIB_PATH):
-        _load_error = (f"mps_bitsandbytes_amd.optim: native library {LIB_PATH} not found. Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}`. There is no Python fallback.")
-        raise RuntimeError(_load_error)
-    try:
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.mbnb_paged_abi_version() != ABI_VERSION:
-            raise OSError(f"ABI version mismatch: library reports {handle.mbnb_paged_abi_version()}, binding expects {ABI_VERSION}")
-    except (OSError, AttributeError) as e:
-        _load_error = f"mps_bitsandbytes_amd.optim: cannot load {LIB_PATH}: {e}"
-        raise RuntimeError(_load_error) from e
-    _lib = handle
-    return _lib
+    return _loader.load(globals())
 
 
 def check(status: int, what: str) -> None:
     if status != 0:
-        msg = lib().mbnb_paged_last_error().decode(errors="replace")
-        raise RuntimeError(f"mps_bitsandbytes_amd.optim.paged.{what} failed (status {status}): {msg}")
+        raise _loader.failed(globals(), status, what)
 
 
 def step(kind: int, dtype: torch.dtype, scalars: Scalars, segments: Sequence[tuple], stream: c_void_p, flags: int = 0) -> None:

@@ -7,17 +7,18 @@ fallback behind it.  If the library is missing or a call fails, the caller gets 
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 from typing import Optional
 
-from . import _native
+from . import _loader, _native
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmbnb_sparse.so")
 
 ABI_VERSION = 1            # include/mbnb_sparse.h MBNB_SPARSE_ABI_VERSION
+_PREFIX, _CHECK_PREFIX = "mbnb_sparse", "mps_bitsandbytes_amd"
+_REQUIRES = (_native,)     # libmbnb_hip.so first: the dependency this library resolves next to itself
 PASS_ONLY = 1              # MBNB_SPARSE_PASS_ONLY: matmul_colrow's dequantising pass alone
 FORCE_GENERIC = 2          # MBNB_SPARSE_FORCE_GENERIC: the generic matmul kernel / the device-built CSR form
 COO_VALUES, COO_INT8_SCALAR, COO_INT8_ENTRY = 0, 1, 2     # value_kind of mbnb_spmm_coo
@@ -47,44 +48,19 @@ _load_error: Optional[str] = None
 
 
 def available() -> bool:
-    try:
-        lib()
-        return True
-    except RuntimeError:
-        return False
+    return _loader.loads(lib)
 
 
 def lib():
     """The loaded library; raises RuntimeError (never falls back) when it cannot be loaded."""
-    global _lib, _load_error
     if _lib is not None:
         return _lib
-    if _load_error is not None:
-        raise RuntimeError(_load_error)
-    if not os.path.exists(LIB_PATH):
-        _load_error = (f"mps_bitsandbytes_amd: native library {LIB_PATH} not found. Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}`. There is no Python fallback.")
-        raise RuntimeError(_load_error)
-    try:
-        _native.lib()          # libmbnb_hip.so first: the dependency this library resolves next to itself
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        if handle.mbnb_sparse_abi_version() != ABI_VERSION:
-            raise OSError(f"ABI version mismatch: library reports {handle.mbnb_sparse_abi_version()}, binding expects {ABI_VERSION}")
-    except (OSError, AttributeError) as e:
-        _load_error = f"mps_bitsandbytes_amd: cannot load {LIB_PATH}: {e}"
-        raise RuntimeError(_load_error) from e
-    _lib = handle
-    return _lib
+    return _loader.load(globals())
 
 
 def check(status: int, what: str) -> None:
     if status != 0:
-        msg = lib().mbnb_sparse_last_error().decode(errors="replace")
-        raise RuntimeError(f"mps_bitsandbytes_amd.{what} failed (status {status}): {msg}")
+        raise _loader.failed(globals(), status, what)
 
 
 def last_kernel() -> str:

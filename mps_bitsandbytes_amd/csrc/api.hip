@@ -10,21 +10,23 @@
 
 #include "common.h"
 #include "dispatch.h"
+#include "host.h"
 
 namespace mbnb {
 
-static thread_local char g_err[512] = "";
 // the last call's kernel name and the variant of its GEMM launch; mbnb_last_kernel() hands out both in one buffer (name, NUL, variant, NUL)
 static thread_local char g_kernel[64] = "";
 static thread_local char g_variant[64] = "";
 static thread_local char g_kernel_out[sizeof(g_kernel) + sizeof(g_variant)] = "";
 
+// this library's error text is host.h's, instantiated in this file alone: the kernel sources write it through these two
 void set_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    vfail(0, fmt, ap);
     va_end(ap);
 }
+int check_launch(const char *what) { return launch_status(what); }
 void set_kernel_name(const char *name) { snprintf(g_kernel, sizeof(g_kernel), "%s", name); }
 void set_kernel_variant(const char *fmt, ...) {
     va_list ap;
@@ -58,27 +60,10 @@ int ensure_dyn_lds(const void *func, int bytes, const char *what) {
     return MBNB_OK;
 }
 
-int check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-        return (int)e;
-    }
-    return MBNB_OK;
-}
-
 static bool dtype_ok(int d) { return d == MBNB_F16 || d == MBNB_BF16 || d == MBNB_F32; }
 static bool qt_ok(int q) { return q == MBNB_NF4 || q == MBNB_FP4; }
 static bool wfmt_ok(int f) { return qt_ok(f) || f == MBNB_W_INT8_ROWWISE || f == MBNB_W_FP8_E4M3 || f == MBNB_W_DENSE; }
 static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 static int absmax_view(const mbnb_absmax *a, const char *who, AbsmaxView &v) {
     if (!a) return fail(MBNB_ERR_ARG, "%s: absmax descriptor is NULL", who);
@@ -101,7 +86,7 @@ extern "C" {
 
 int mbnb_abi_version(void) { return MBNB_ABI_VERSION; }
 
-const char *mbnb_last_error(void) { return g_err; }
+const char *mbnb_last_error(void) { return last_error(); }
 const char *mbnb_last_kernel(void) {
     const size_t n = strlen(g_kernel) + 1;
     memcpy(g_kernel_out, g_kernel, n);

@@ -5,13 +5,11 @@
 #include <stdint.h>
 
 #include "../../include/mbnb_hip.h"
+#include "elem_types.h"
 
 namespace mbnb {
 
-// ---------------------------------------------------------------- element types
-using f16_t = _Float16;
-using bf16_t = __bf16;
-
+// ---------------------------------------------------------------- element types (f16_t, bf16_t: elem_types.h)
 template <int DT> struct ElemT;
 template <> struct ElemT<MBNB_F16> { using type = f16_t; };
 template <> struct ElemT<MBNB_BF16> { using type = bf16_t; };

@@ -9,17 +9,14 @@
 //   `.sqrt()` and every division correctly rounded; `.round()` half to even.
 // Non-finite inputs are outside that contract: a NaN moment is stored as code 0 and a NaN is never a block
 // maximum (fmaxf drops it); an infinite maximum gives codes 0 for its block.  Nothing here can fault on them.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/mbnb_optim.h"
+#include "host.h"
 
 namespace {
 
-using f16_t = _Float16;
-using bf16_t = __bf16;
+using mbnb::bf16_t;
+using mbnb::f16_t;
+using mbnb::fail;
 
 constexpr int kThreads = 256;          // every launch: 4 waves
 constexpr int kFastBlock = 256;        // the wave-per-block path: 64 lanes x 4 elements
@@ -261,16 +258,6 @@ __global__ __launch_bounds__(kThreads) void k_optim8_generic(const OptimArgs a) 
 }
 
 // ---------------------------------------------------------------- host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 template <int KIND, typename PT, typename GT>
 int launch(const OptimArgs &a, bool generic, hipStream_t stream) {
     const int64_t blocks = a.first_block[a.n];
@@ -281,9 +268,7 @@ int launch(const OptimArgs &a, bool generic, hipStream_t stream) {
         hipLaunchKernelGGL((k_optim8_generic<KIND, PT, GT>), dim3((unsigned)grid), dim3(kThreads), 0, stream, a);
     else
         hipLaunchKernelGGL((k_optim8_wave<KIND, PT, GT>), dim3((unsigned)grid), dim3(kThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "mbnb_optim_step: kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return mbnb::launch_status("mbnb_optim_step");
 }
 
 template <typename PT, typename GT>
@@ -309,7 +294,7 @@ extern "C" {
 
 int mbnb_optim_abi_version(void) { return MBNB_OPTIM_ABI_VERSION; }
 
-const char *mbnb_optim_last_error(void) { return g_err; }
+const char *mbnb_optim_last_error(void) { return mbnb::last_error(); }
 
 int mbnb_optim_step(int kind, int param_dtype, int grad_dtype, int64_t block_size, const mbnb_optim_scalars *scalars,
                     const mbnb_optim_tensor *table, int n, int flags, void *stream) {

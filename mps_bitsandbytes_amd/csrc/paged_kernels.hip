@@ -9,17 +9,14 @@
 //   `.sqrt()` and every division correctly rounded, true divisions, no reciprocals.
 // The kernel is purely elementwise over *segments* (element ranges of tensors) and knows nothing about paging: the
 // moment pointers are a tensor's own storage or a staging slot.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/mbnb_paged.h"
+#include "host.h"
 
 namespace {
 
-using f16_t = _Float16;
-using bf16_t = __bf16;
+using mbnb::bf16_t;
+using mbnb::f16_t;
+using mbnb::fail;
 
 constexpr int kThreads = 256;          // every launch: 4 waves
 constexpr int kChunks = 4;             // 16-byte chunks per thread and stream: a workgroup covers 16 KiB of each tensor
@@ -148,25 +145,13 @@ __global__ __launch_bounds__(kThreads) void k_paged_step(const PagedArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 template <int KIND, typename T>
 int launch(const PagedArgs &a, hipStream_t stream) {
     const int64_t blocks = a.first_block[a.n];
     if (blocks == 0) return 0;
     if (blocks > INT32_MAX) return fail(MBNB_PAGED_ERR_SHAPE, "mbnb_paged_step: %lld workgroups exceed one launch", (long long)blocks);
     hipLaunchKernelGGL((k_paged_step<KIND, T>), dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "mbnb_paged_step: kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return mbnb::launch_status("mbnb_paged_step");
 }
 
 template <typename T>
@@ -184,7 +169,7 @@ extern "C" {
 
 int mbnb_paged_abi_version(void) { return MBNB_PAGED_ABI_VERSION; }
 
-const char *mbnb_paged_last_error(void) { return g_err; }
+const char *mbnb_paged_last_error(void) { return mbnb::last_error(); }
 
 int mbnb_paged_step(int kind, int dtype, const mbnb_paged_scalars *scalars, const mbnb_paged_segment *table, int n, int flags,
                     void *stream) {

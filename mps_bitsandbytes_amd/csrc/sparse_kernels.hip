@@ -3,23 +3,31 @@
 //   COO sparse operations               dense -> COO, int8 values with one absmax scale, out = sparse . dense through a CSR form
 // The MFMA work of matmul_colrow's dense route is libmbnb_hip's public mbnb_gemm_dense with the library's own plan (slices = 0); this
 // file holds the passes around it and every other kernel.  Its own last-error and kernel-name records (mbnb_sparse_last_*).
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <type_traits>
 
 #include "../../include/mbnb_sparse.h"
 #include "common.h"
+#include "host.h"
+
+// host.h's predicates and with_dtype() take this library's dtype codes
+static_assert(MBNB_SPARSE_F16 == mbnb::kF16 && MBNB_SPARSE_BF16 == mbnb::kBF16 && MBNB_SPARSE_F32 == mbnb::kF32, "dtype codes");
 
 namespace {
 
+using mbnb::aligned;
 using mbnb::bf16_t;
+using mbnb::esize;
 using mbnb::f16_t;
+using mbnb::fail;
 using mbnb::from_f32;
+using mbnb::is16;
+using mbnb::kMaxElems;
 using mbnb::pack2;
+using mbnb::round256;
 using mbnb::to_f32;
 using mbnb::u32x2;
 using mbnb::u32x4;
+using mbnb::with_dtype;
 
 // ---------------------------------------------------------------- small device helpers
 // |v| as its bit pattern.  For non-negative floats the unsigned order of the patterns is the order of the values, +Inf above every finite
@@ -596,40 +604,16 @@ enum { KN_CR_Q8, KN_CR_Q1, KN_CR_DQ8, KN_CR_DQ1, KN_CR_DENSE, KN_CR_GENERIC, KN_
 const char *const kSparseKernelNames[] = {"colrow_quantize8", "colrow_quantize1", "colrow_dequant8", "colrow_dequant1", "colrow_dq+dense", "colrow_generic",
                                           "coo_count", "coo_fill", "coo_quantize", "spmm_coo8", "spmm_coo1", "spmm_coo8_general", "spmm_coo1_general"};
 
-thread_local char g_err[512] = "";
 thread_local const char *g_kernel = "";
 
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 int launched(const char *what, int name) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
+    if (int rc = mbnb::launch_status(what)) return rc;
     g_kernel = kSparseKernelNames[name];
     return MBNB_SPARSE_OK;
 }
 
 bool dtype_ok(int dtype) { return dtype >= MBNB_SPARSE_F16 && dtype <= MBNB_SPARSE_F32; }
-bool is16(int dtype) { return dtype == MBNB_SPARSE_F16 || dtype == MBNB_SPARSE_BF16; }
-int esize(int dtype) { return dtype == MBNB_SPARSE_F32 ? 4 : 2; }
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-int64_t round256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-constexpr int64_t kMaxElems = (int64_t)1 << 38;   // element counts: every flat grid of 256-thread workgroups stays below 2^31
 constexpr int64_t kMaxGrid = 0x7FFFFFFF;
-
-// dispatch on the element type: f(T{}) with T = f16_t / bf16_t / float
-template <typename F> int with_dtype(int dtype, F &&f) {
-    switch (dtype) {
-        case MBNB_SPARSE_F16: return f(f16_t{});
-        case MBNB_SPARSE_BF16: return f(bf16_t{});
-        default: return f(float{});
-    }
-}
 
 // ---- col + row
 int64_t cr_chunks(int64_t C) { return (C + CR_CB - 1) / CR_CB; }
@@ -693,7 +677,7 @@ constexpr int64_t kMaxIndex = 0x7FFFFFFE;
 extern "C" {
 
 int mbnb_sparse_abi_version(void) { return MBNB_SPARSE_ABI_VERSION; }
-const char *mbnb_sparse_last_error(void) { return g_err; }
+const char *mbnb_sparse_last_error(void) { return mbnb::last_error(); }
 const char *mbnb_sparse_last_kernel(void) { return g_kernel; }
 
 // --------------------------------------------------------------------------- col + row

@@ -3,23 +3,31 @@
 //   the weight gradient               dW = dY^T . X   (a contraction over the token dimension M)
 // The MFMA work is libmbnb_hip's public mbnb_gemm_dense with the library's own plan (slices = 0); this file holds the passes that
 // feed it and the generic kernels for what it does not take.  Its own last-error and kernel-name records (mbnb_train_last_*).
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <type_traits>
 
 #include "../../include/mbnb_train.h"
 #include "common.h"
+#include "host.h"
+
+// host.h's predicates and with_dtype() take this library's dtype codes
+static_assert(MBNB_TRAIN_F16 == mbnb::kF16 && MBNB_TRAIN_BF16 == mbnb::kBF16 && MBNB_TRAIN_F32 == mbnb::kF32, "dtype codes");
 
 namespace {
 
+using mbnb::aligned;
 using mbnb::bf16_t;
+using mbnb::esize;
 using mbnb::f16_t;
+using mbnb::fail;
 using mbnb::from_f32;
+using mbnb::is16;
+using mbnb::kMaxElems;
 using mbnb::pack2;
+using mbnb::round256;
 using mbnb::to_f32;
 using mbnb::u32x2;
 using mbnb::u32x4;
+using mbnb::with_dtype;
 
 // ---------------------------------------------------------------- the SwitchBack weight rule (reference SwitchBackFunction.forward)
 // `weight_int8.to(T) * (weight_scales[:, None] / 127.0).to(T)`: the quotient in f32, rounded to T, times the code, rounded to T again.
@@ -216,20 +224,10 @@ __global__ __launch_bounds__(256) void k_grad_w_generic(const T *__restrict__ dY
 enum { KN_SB_DQ, KN_SB_DENSE, KN_SB_GENERIC, KN_GW_T, KN_GW_DENSE, KN_GW_GENERIC };
 const char *const kTrainKernelNames[] = {"switchback_dq", "switchback_dq+dense", "switchback_generic", "grad_w_t", "grad_w_t+dense", "grad_w_generic"};
 
-thread_local char g_err[512] = "";
 thread_local const char *g_kernel = "";
 
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 int launched(const char *what, int name) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "%s: kernel launch failed: %s", what, hipGetErrorString(e));
+    if (int rc = mbnb::launch_status(what)) return rc;
     g_kernel = kTrainKernelNames[name];
     return MBNB_TRAIN_OK;
 }
@@ -238,12 +236,6 @@ int from_gemm(int rc, const char *what) {
     if (rc != 0) return fail(rc, "%s: mbnb_gemm_dense failed: %s", what, mbnb_last_error());
     return MBNB_TRAIN_OK;
 }
-
-bool is16(int dtype) { return dtype == MBNB_TRAIN_F16 || dtype == MBNB_TRAIN_BF16; }
-int esize(int dtype) { return dtype == MBNB_TRAIN_F32 ? 4 : 2; }
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-int64_t round256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-constexpr int64_t kMaxElems = (int64_t)1 << 38;   // element counts: every flat grid of 256-thread workgroups stays below 2^31
 
 // Route thresholds, measured with MBNB_TRAIN_FORCE_GENERIC against the default: the generic kernels win only on
 // small products.  The forward takes the dense route from 2^27 multiply-adds, and below M = 16 only on weights of 2^25 elements or more
@@ -377,11 +369,10 @@ int gw_dispatch(const void *dY, const void *X, int64_t M, int64_t N, int64_t K, 
         g_kernel = kTrainKernelNames[KN_GW_DENSE];
         return MBNB_TRAIN_OK;
     }
-    switch (dtype) {
-        case MBNB_TRAIN_F16: return gw_generic<f16_t>(static_cast<const f16_t *>(dY), static_cast<const f16_t *>(X), M, N, K, static_cast<f16_t *>(dW), st);
-        case MBNB_TRAIN_BF16: return gw_generic<bf16_t>(static_cast<const bf16_t *>(dY), static_cast<const bf16_t *>(X), M, N, K, static_cast<bf16_t *>(dW), st);
-        default: return gw_generic<float>(static_cast<const float *>(dY), static_cast<const float *>(X), M, N, K, static_cast<float *>(dW), st);
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return gw_generic<T>(static_cast<const T *>(dY), static_cast<const T *>(X), M, N, K, static_cast<T *>(dW), st);
+    });
 }
 
 bool dtype_ok(int dtype) { return dtype >= MBNB_TRAIN_F16 && dtype <= MBNB_TRAIN_F32; }
@@ -391,7 +382,7 @@ bool dtype_ok(int dtype) { return dtype >= MBNB_TRAIN_F16 && dtype <= MBNB_TRAIN
 extern "C" {
 
 int mbnb_train_abi_version(void) { return MBNB_TRAIN_ABI_VERSION; }
-const char *mbnb_train_last_error(void) { return g_err; }
+const char *mbnb_train_last_error(void) { return mbnb::last_error(); }
 const char *mbnb_train_last_kernel(void) { return g_kernel; }
 int64_t mbnb_train_padded_rows(int64_t M) { return M < 0 ? 0 : padded_rows(M); }
 
@@ -422,17 +413,11 @@ int mbnb_switchback_forward(const void *X, int dtype, int64_t M, int64_t K, cons
     if (!aligned(out, esize(dtype)) || (!pass && (!aligned(X, esize(dtype)) || (bias && !aligned(bias, esize(dtype))))))
         return fail(MBNB_TRAIN_ERR_ARG, "switchback_forward: X, bias and out must be aligned to their element size");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case MBNB_TRAIN_F16:
-            return sb_forward<f16_t>(static_cast<const f16_t *>(X), M, K, W, scales, N, static_cast<const f16_t *>(bias), static_cast<f16_t *>(out),
-                                     workspace, workspace_bytes, flags, st);
-        case MBNB_TRAIN_BF16:
-            return sb_forward<bf16_t>(static_cast<const bf16_t *>(X), M, K, W, scales, N, static_cast<const bf16_t *>(bias), static_cast<bf16_t *>(out),
-                                      workspace, workspace_bytes, flags, st);
-        default:
-            return sb_forward<float>(static_cast<const float *>(X), M, K, W, scales, N, static_cast<const float *>(bias), static_cast<float *>(out),
-                                     workspace, workspace_bytes, flags, st);
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return sb_forward<T>(static_cast<const T *>(X), M, K, W, scales, N, static_cast<const T *>(bias), static_cast<T *>(out), workspace, workspace_bytes,
+                             flags, st);
+    });
 }
 
 int64_t mbnb_linear_grad_weight_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype) {

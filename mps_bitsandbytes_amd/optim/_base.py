@@ -1,5 +1,6 @@
-"""Machinery shared by the 8-bit optimizers: state dtypes across load_state_dict, parameter checks, and one fused HIP
-step per (parameter dtype, gradient dtype) pair of a group (libmbnb_optim.so; no CPU path)."""
+"""Machinery shared by the optimizers.  FusedOptimizer: what the 8-bit and the paged ones have in common (hyper-parameter and gradient
+checks, staging of operands a kernel cannot take in place).  Optimizer8bit: state dtypes across load_state_dict, state checks, and one
+fused HIP step per (parameter dtype, gradient dtype) pair of a group (libmbnb_optim.so; no CPU path)."""
 import numbers
 from collections import defaultdict
 from typing import Dict, List, Tuple
@@ -31,7 +32,68 @@ def _aligned(t: torch.Tensor) -> bool:
     return t.is_contiguous() and t.data_ptr() % 16 == 0
 
 
-class Optimizer8bit(Optimizer):
+def check_hyper(lr=None, eps=None, betas=None, weight_decay=None) -> None:
+    """The constructors' range checks, with the reference's texts; an optimizer passes the hyper-parameters it has."""
+    if lr is not None and lr < 0.0:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if eps is not None and eps < 0.0:
+        raise ValueError(f"Invalid epsilon: {eps}")
+    if betas is not None:
+        for i in (0, 1):
+            if not 0.0 <= betas[i] < 1.0:
+                raise ValueError(f"Invalid beta{i + 1}: {betas[i]}")
+    if weight_decay is not None and weight_decay < 0.0:
+        raise ValueError(f"Invalid weight_decay: {weight_decay}")
+
+
+class FusedOptimizer(Optimizer):
+    """Base of the 8-bit and the paged optimizers: a step hands raw pointers of parameters and gradients to one fused kernel."""
+
+    _name = "FusedOptimizer"
+    _f32_grads = True      # a gradient may be float32 beside a 16-bit parameter (the 8-bit kernels); False: the parameter's dtype alone
+
+    def _grads(self, group) -> List[torch.nn.Parameter]:
+        """The group's parameters that have a gradient, checked (sparse, device, dtypes)."""
+        out = []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError(f"{self._name} does not support sparse gradients")
+            _check_device(p, self._name)
+            _check_device(p.grad, self._name)
+            _native.dtype_code(p.dtype, self._name)
+            if p.grad.dtype != p.dtype and not (self._f32_grads and p.grad.dtype == torch.float32):
+                rule = "be the parameter's dtype or float32" if self._f32_grads else "have the parameter's dtype"
+                raise TypeError(f"mps_bitsandbytes_amd {self._name}: gradient dtype {p.grad.dtype} does not go with parameter "
+                                f"dtype {p.dtype} (the gradient must {rule})")
+            if p.grad.device != p.device:
+                raise ValueError(f"mps_bitsandbytes_amd {self._name}: gradient on {p.grad.device}, parameter on {p.device}")
+            out.append(p)
+        return out
+
+    @staticmethod
+    def _stage(params) -> Tuple[list, list]:
+        """(parameter, gradient) as the kernel can address them, per parameter: itself where it is contiguous and 16-byte aligned, else a
+        clone.  Also the (parameter, clone) pairs to copy back after the launch (_unstage); the caller keeps the first list until then."""
+        staged, writeback = [], []
+        for p in params:
+            w, g = p, p.grad
+            if not _aligned(w):
+                w = p.detach().clone(memory_format=torch.contiguous_format)
+                writeback.append((p, w))
+            if not _aligned(g):
+                g = g.clone(memory_format=torch.contiguous_format)
+            staged.append((w, g))
+        return staged, writeback
+
+    @staticmethod
+    def _unstage(writeback) -> None:
+        for p, w in writeback:
+            p.copy_(w)
+
+
+class Optimizer8bit(FusedOptimizer):
     """Base of Adam8bit / AdamW8bit / Lion8bit / SGD8bit."""
 
     _name = "Optimizer8bit"
@@ -58,25 +120,6 @@ class Optimizer8bit(Optimizer):
                 st[k] = w.clone() if w is v else w      # never share state tensors with the optimizer the dict came from
             if "step" in st and isinstance(st["step"], torch.Tensor):
                 st["step"] = int(st["step"].item())
-
-    def _grads(self, group) -> List[torch.nn.Parameter]:
-        """The group's parameters that have a gradient, checked (sparse, device, dtypes)."""
-        out = []
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            if p.grad.is_sparse:
-                raise RuntimeError(f"{self._name} does not support sparse gradients")
-            _check_device(p, self._name)
-            _check_device(p.grad, self._name)
-            _native.dtype_code(p.dtype, self._name)
-            if p.grad.dtype not in (p.dtype, torch.float32):
-                raise TypeError(f"mps_bitsandbytes_amd {self._name}: gradient dtype {p.grad.dtype} does not go with parameter "
-                                f"dtype {p.dtype} (the gradient must be the parameter's dtype or float32)")
-            if p.grad.device != p.device:
-                raise ValueError(f"mps_bitsandbytes_amd {self._name}: gradient on {p.grad.device}, parameter on {p.device}")
-            out.append(p)
-        return out
 
     def _block_size(self, group) -> int:
         block_size = group["block_size"]
@@ -107,22 +150,14 @@ class Optimizer8bit(Optimizer):
             p = it[0]
             buckets[(p.device, p.dtype, p.grad.dtype)].append(it)
         for (dev, pdt, gdt), its in buckets.items():
-            descs, writeback, keep = [], [], []
-            for p, (c1, m1, c2, m2), bc2, nss in its:
-                work, g = p, p.grad
-                if not _aligned(work):
-                    work = p.detach().clone(memory_format=torch.contiguous_format)
-                    writeback.append((p, work))
-                if not _aligned(g):
-                    g = g.clone(memory_format=torch.contiguous_format)
-                    keep.append(g)
-                descs.append((work.data_ptr(), g.data_ptr(), c1.data_ptr(), m1.data_ptr(),
-                              0 if c2 is None else c2.data_ptr(), 0 if m2 is None else m2.data_ptr(), work.numel(), bc2, nss))
+            staged, writeback = self._stage([it[0] for it in its])
+            descs = [(w.data_ptr(), g.data_ptr(), c1.data_ptr(), m1.data_ptr(), 0 if c2 is None else c2.data_ptr(),
+                      0 if m2 is None else m2.data_ptr(), w.numel(), bc2, nss)
+                     for (w, g), (_, (c1, m1, c2, m2), bc2, nss) in zip(staged, its)]
             with _native.on_device(dev):
                 _optim_native.step(kind, pdt, gdt, block_size, scalars_for(pdt, gdt), descs, _native.stream_ptr(dev),
                                    self._step_flags)
-            for p, work in writeback:
-                p.copy_(work)
+            self._unstage(writeback)
 
 
 def check_state(p: torch.Tensor, tensors, block_size: int, name: str, two_moments: bool = False) -> None:

@@ -11,7 +11,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from .. import _optim_native
-from ._base import Optimizer8bit, f32, new_state
+from ._base import Optimizer8bit, check_hyper, f32, new_state
 
 
 # ---------------------------------------------------------------- state codes (torch ops: utilities, not the step)
@@ -68,16 +68,7 @@ class _Adam8bitBase(Optimizer8bit):
     _kind = _optim_native.ADAM
 
     def __init__(self, params, lr, betas, eps, weight_decay, block_size, max_grad_norm):
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if eps < 0.0:
-            raise ValueError(f"Invalid epsilon: {eps}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta1: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta2: {betas[1]}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay: {weight_decay}")
+        check_hyper(lr=lr, eps=eps, betas=betas, weight_decay=weight_decay)
         if max_grad_norm is not None and max_grad_norm <= 0.0:
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,

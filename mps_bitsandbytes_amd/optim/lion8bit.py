@@ -4,7 +4,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from .. import _optim_native
-from ._base import Optimizer8bit, f32, in_dtype, new_state
+from ._base import Optimizer8bit, check_hyper, f32, in_dtype, new_state
 
 
 class Lion8bit(Optimizer8bit):
@@ -22,14 +22,7 @@ class Lion8bit(Optimizer8bit):
 
     def __init__(self, params, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.99), weight_decay: float = 0,
                  block_size: int = 256):
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta1: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta2: {betas[1]}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay: {weight_decay}")
+        check_hyper(lr=lr, betas=betas, weight_decay=weight_decay)
         defaults = dict(lr=lr, betas=betas, weight_decay=weight_decay, block_size=block_size)
         super().__init__(params, defaults)
 

@@ -17,11 +17,9 @@ from collections import defaultdict
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
-from torch.optim import Optimizer
 
 from .. import _native, _paged_native
-from ..functional import _check_device
-from ._base import _aligned, f32, in_dtype
+from ._base import FusedOptimizer, check_hyper, f32, in_dtype
 
 PAGE_ALIGN = 8             # elements: every segment starts on a multiple of 8 elements of its tensor (16 bytes of a 16-bit dtype)
 _MOMENTS = ("exp_avg", "exp_avg_sq")
@@ -87,8 +85,9 @@ class _Ring:
         self.next = 0
 
 
-class _PagedBase(Optimizer):
+class _PagedBase(FusedOptimizer):
     _name = "PagedOptimizer"
+    _f32_grads = False     # a gradient has its parameter's dtype
     _kind = _paged_native.ADAMW
     _moments = 2
     _page_elems = 1 << 26  # elements per page (chosen from tools/paged_bench.py's sweep)
@@ -164,25 +163,6 @@ class _PagedBase(Optimizer):
             out.append(h)
         return out
 
-    def _grads(self, group) -> List[torch.nn.Parameter]:
-        """The group's parameters that have a gradient, checked (sparse, device, dtype)."""
-        out = []
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            if p.grad.is_sparse:
-                raise RuntimeError(f"{self._name} does not support sparse gradients")
-            _check_device(p, self._name)
-            _check_device(p.grad, self._name)
-            _native.dtype_code(p.dtype, self._name)
-            if p.grad.dtype != p.dtype:
-                raise TypeError(f"mps_bitsandbytes_amd {self._name}: gradient dtype {p.grad.dtype} does not go with parameter dtype "
-                                f"{p.dtype} (the gradient must have the parameter's dtype)")
-            if p.grad.device != p.device:
-                raise ValueError(f"mps_bitsandbytes_amd {self._name}: gradient on {p.grad.device}, parameter on {p.device}")
-            out.append(p)
-        return out
-
     # ------------------------------------------------------------------ the step
     def _run(self, group, items: List[tuple], scalars_for) -> None:
         """items: (param, [moments], bc2_sqrt, neg_step_size) per parameter with a gradient."""
@@ -191,16 +171,8 @@ class _PagedBase(Optimizer):
         for it in items:
             buckets[(it[0].device, it[0].dtype)].append(it)
         for (dev, dt), its in buckets.items():
-            work, writeback, keep = [], [], []
-            for p, moments, bc2, nss in its:
-                w, g = p, p.grad
-                if not _aligned(w):
-                    w = p.detach().clone(memory_format=torch.contiguous_format)
-                    writeback.append((p, w))
-                if not _aligned(g):
-                    g = g.clone(memory_format=torch.contiguous_format)
-                    keep.append(g)
-                work.append((w, g, moments, bc2, nss))
+            staged, writeback = self._stage([it[0] for it in its])
+            work = [(w, g, moments, bc2, nss) for (w, g), (_, moments, bc2, nss) in zip(staged, its)]
             with _native.on_device(dev):
                 if paged:
                     self._step_paged(dev, dt, work, scalars_for(dt))
@@ -208,8 +180,7 @@ class _PagedBase(Optimizer):
                     segs = [(w.data_ptr(), g.data_ptr(), ms[0].data_ptr(), ms[1].data_ptr() if len(ms) > 1 else 0, w.numel(), bc2, nss)
                             for w, g, ms, bc2, nss in work]
                     _paged_native.step(self._kind, dt, scalars_for(dt), segs, _native.stream_ptr(dev), self._step_flags)
-            for p, w in writeback:
-                p.copy_(w)
+            self._unstage(writeback)
 
     def _ring(self, dev) -> _Ring:
         page = int(self._page_elems)
@@ -281,16 +252,7 @@ class PagedAdamW(_PagedBase):
 
     def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, page_to_cpu: bool = True):
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if eps < 0.0:
-            raise ValueError(f"Invalid epsilon: {eps}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta1: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta2: {betas[1]}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay: {weight_decay}")
+        check_hyper(lr=lr, eps=eps, betas=betas, weight_decay=weight_decay)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, page_to_cpu=page_to_cpu)
         super().__init__(params, defaults)
         self._init_paging()
@@ -359,12 +321,7 @@ class PagedLion(_PagedBase):
 
     def __init__(self, params, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.99), weight_decay: float = 0,
                  page_to_cpu: bool = True):
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta1: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta2: {betas[1]}")
+        check_hyper(lr=lr, betas=betas)
         defaults = dict(lr=lr, betas=betas, weight_decay=weight_decay, page_to_cpu=page_to_cpu)
         super().__init__(params, defaults)
         self._init_paging()

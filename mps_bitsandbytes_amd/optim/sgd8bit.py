@@ -5,7 +5,7 @@ from typing import Callable, Optional
 import torch
 
 from .. import _optim_native
-from ._base import Optimizer8bit, f32, in_dtype, new_state
+from ._base import Optimizer8bit, check_hyper, f32, in_dtype, new_state
 
 
 class SGD8bit(Optimizer8bit):
@@ -25,12 +25,10 @@ class SGD8bit(Optimizer8bit):
 
     def __init__(self, params, lr: float, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
                  nesterov: bool = False, block_size: int = 256):
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
+        check_hyper(lr=lr)
         if momentum < 0.0:
             raise ValueError(f"Invalid momentum: {momentum}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay: {weight_decay}")
+        check_hyper(weight_decay=weight_decay)
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires momentum > 0 and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,

@@ -8,7 +8,7 @@ import re
 import pytest
 import torch
 
-from mps_bitsandbytes_amd import _native
+from mps_bitsandbytes_amd import _native, _optim_native, _paged_native, _sparse_native, _train_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -158,10 +158,60 @@ def test_product_has_no_cpu_path_and_never_imports_the_oracle():
                 assert "liboracle" not in src, f"{f} references the oracle library"
 
 
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
+# ----------------------------------------------------------------------------- the load path, the same for all five binding modules
+BINDINGS = [_native, _optim_native, _train_native, _sparse_native, _paged_native]
+_ids = lambda m: m.__name__.rsplit(".", 1)[1]
+
+
+@pytest.mark.parametrize("binding", BINDINGS, ids=_ids)
+def test_missing_library_fails_loudly(binding, monkeypatch, tmp_path):
+    monkeypatch.setattr(binding, "_lib", None)
+    monkeypatch.setattr(binding, "_load_error", None)
+    monkeypatch.setattr(binding, "LIB_PATH", str(tmp_path / "nope.so"))
+    with pytest.raises(RuntimeError, match="no Python fallback") as e:
+        binding.lib()
+    assert binding.available() is False
+    msg = str(e.value)
+    assert str(tmp_path / "nope.so") in msg and "make -C " in msg and "build()" in msg and msg.endswith("There is no Python fallback.")
+
+
+@pytest.mark.parametrize("binding", BINDINGS, ids=_ids)
+def test_abi_version_mismatch_is_refused_and_cached(binding, monkeypatch):
+    binding.lib()                                        # (and, for train and sparse, the main library they need)
+    monkeypatch.setattr(binding, "_lib", None)
+    monkeypatch.setattr(binding, "_load_error", None)
+    monkeypatch.setattr(binding, "ABI_VERSION", 999)
+    with pytest.raises(RuntimeError, match="ABI version mismatch") as first:
+        binding.lib()
+    assert "binding expects 999" in str(first.value)
+    assert binding.available() is False
+
+    def no_load(*a, **k):
+        raise AssertionError("a second load attempt")
+
+    monkeypatch.setattr(ctypes, "CDLL", no_load)
+    with pytest.raises(RuntimeError) as second:
+        binding.lib()
+    assert str(second.value) == str(first.value)
+
+
+@pytest.mark.parametrize("binding", [_train_native, _sparse_native], ids=_ids)
+def test_the_main_library_is_loaded_first(binding, monkeypatch, tmp_path):
+    missing = str(tmp_path / "libmbnb_hip.so")
     monkeypatch.setattr(_native, "_lib", None)
     monkeypatch.setattr(_native, "_load_error", None)
-    monkeypatch.setattr(_native, "LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no Python fallback"):
-        _native.lib()
-    assert _native.available() is False
+    monkeypatch.setattr(_native, "LIB_PATH", missing)
+    monkeypatch.setattr(binding, "_lib", None)
+    monkeypatch.setattr(binding, "_load_error", None)
+    with pytest.raises(RuntimeError, match="no Python fallback") as e:
+        binding.lib()
+    assert missing in str(e.value) and binding.LIB_PATH not in str(e.value)
+
+
+@pytest.mark.parametrize("binding, prefix", list(zip(BINDINGS, [
+    "mps_bitsandbytes_amd.unit", "mps_bitsandbytes_amd.optim.unit", "mps_bitsandbytes_amd.unit", "mps_bitsandbytes_amd.unit",
+    "mps_bitsandbytes_amd.optim.paged.unit"])), ids=[_ids(m) for m in BINDINGS])
+def test_check_raises_with_the_modules_prefix(binding, prefix):
+    binding.check(0, "unit")
+    with pytest.raises(RuntimeError, match=r"^" + re.escape(prefix) + r" failed \(status -1\): "):
+        binding.check(-1, "unit")

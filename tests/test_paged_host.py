@@ -175,15 +175,6 @@ def test_argument_errors_return_a_status_before_any_device_access():
         pn.check(-1, "unit")
 
 
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    monkeypatch.setattr(_paged_native, "_lib", None)
-    monkeypatch.setattr(_paged_native, "_load_error", None)
-    monkeypatch.setattr(_paged_native, "LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no Python fallback"):
-        _paged_native.lib()
-    assert _paged_native.available() is False
-
-
 # ----------------------------------------------------------------------------- the page plan
 def _check_plan(numels, page_elems):
     pages = paged.plan_pages(numels, page_elems)
