@@ -42,7 +42,14 @@ enum { MBNB_SPARSE_OK = 0, MBNB_SPARSE_ERR_ARG = -1, MBNB_SPARSE_ERR_SHAPE = -2,
 int mbnb_sparse_abi_version(void);
 /* thread-local, never NULL; valid until the next failing call on this thread */
 const char *mbnb_sparse_last_error(void);
-/* name of the kernel route the last successful call on this thread took ("colrow_quantize8", "spmm_coo8", ...) */
+/* name of the kernel route the last successful call on this thread took ("colrow_quantize8", "spmm_coo8", ...).
+ * The pointer leads into a thread-local buffer that holds TWO strings: the name, its terminating NUL, then the VARIANT of the call
+ * and a second NUL -- what the name does not say about the kernel forms that ran, "" where the launcher sets none:
+ *   "wt"          colrow_dequant8 of a 16-bit dtype with write-through stores (matmul_colrow's dense route and its pass alone)
+ *   "parts<n>"    coo_quantize: the number of partial maxima = workgroups, min(ceil(nnz / 2048), 1024)
+ *   "G<g> x<t>"   spmm_coo*: g = 16 | 32 | 64 lanes per output row, t column tiles of g * (vector: 16 / sizeof(T), scalar: 4) columns
+ * The variant of the "+dense" route's GEMM stays in mbnb_last_kernel()'s buffer.  A reader of the name alone sees what it always saw;
+ * the variant is at `p + strlen(p) + 1`.  Valid until the next call on this thread. */
 const char *mbnb_sparse_last_kernel(void);
 
 /* ---------------------------------------------------------------------------

@@ -40,7 +40,16 @@ enum { MBNB_TRAIN_OK = 0, MBNB_TRAIN_ERR_ARG = -1, MBNB_TRAIN_ERR_SHAPE = -2, MB
 int mbnb_train_abi_version(void);
 /* thread-local, never NULL; valid until the next failing call on this thread */
 const char *mbnb_train_last_error(void);
-/* name of the kernel route the last successful call on this thread took ("switchback_dq+dense", "grad_w_generic", ...) */
+/* name of the kernel route the last successful call on this thread took ("switchback_dq+dense", "grad_w_generic", ...).
+ * The pointer leads into a thread-local buffer that holds TWO strings: the name, its terminating NUL, then the VARIANT of the call
+ * and a second NUL -- the kernel forms that ran behind the name, as words joined by blanks, "" where the launcher sets none:
+ *   the Wd pass          "dq8x4" (vector form, 4 rows per thread: N K <= 2^25 and (N + 3) / 4 <= 65535) | "dq8x1" (one row: N <= 65535) |
+ *                        "dq1" (scalar: f32, K % 8 != 0, W off 8 or the output off 16 bytes, or N > 65535)
+ *   the bias pass        "bias8" (N % 8 == 0 and a 16-byte aligned bias) | "bias1" | "nobias", behind the Wd pass's word
+ *   the transposing pass "dy8" | "dy1" for dY, "x8" | "x1" for X (8: C % 8 == 0 and a 16-byte aligned operand)
+ * so "dq8x4 bias8", "dy1 x8", "x1" (the pass alone).  The generic kernels set none; the variant of a "+dense" route's GEMM stays in
+ * mbnb_last_kernel()'s buffer.  A reader of the name alone sees what it always saw; the variant is at `p + strlen(p) + 1`.  Valid
+ * until the next call on this thread. */
 const char *mbnb_train_last_kernel(void);
 
 /* ---------------------------------------------------------------------------

@@ -7,6 +7,7 @@ fallback behind it.  If the library is missing or a call fails, the caller gets 
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from ctypes import c_char_p, c_int, c_int64, c_void_p
 from typing import Optional
@@ -59,6 +60,19 @@ def check(status: int, what: str) -> None:
 def last_kernel() -> str:
     """The kernel route the last call on this thread took (mbnb_train_last_kernel)."""
     return lib().mbnb_train_last_kernel().decode()
+
+
+_last_kernel_addr = None
+
+
+def last_variant() -> str:
+    """The variant of the last call ("dq8x4 bias8", "dy1 x8"; "" where the launcher sets none): the second string of
+    mbnb_train_last_kernel()'s buffer, right behind the name's terminating NUL (include/mbnb_train.h)."""
+    global _last_kernel_addr
+    if _last_kernel_addr is None:
+        _last_kernel_addr = ctypes.CFUNCTYPE(c_void_p)(("mbnb_train_last_kernel", lib()))    # the same export, its pointer kept as an address
+    addr = _last_kernel_addr()
+    return ctypes.string_at(addr + len(ctypes.string_at(addr)) + 1).decode()
 
 
 def padded_rows(M: int) -> int:

@@ -3,6 +3,9 @@
 //   COO sparse operations               dense -> COO, int8 values with one absmax scale, out = sparse . dense through a CSR form
 // The MFMA work of matmul_colrow's dense route is libmbnb_hip's public mbnb_gemm_dense with the library's own plan (slices = 0); this
 // file holds the passes around it and every other kernel.  Its own last-error and kernel-name records (mbnb_sparse_last_*).
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 #include "../../include/mbnb_sparse.h"
@@ -606,8 +609,28 @@ const char *const kSparseKernelNames[] = {"colrow_quantize8", "colrow_quantize1"
 
 thread_local const char *g_kernel = "";
 
+// The variant of the last call: what the name does not say about the kernel forms that ran ("wt", "parts1024", "G16 x2"; tests/
+// int8_decomp_cases.py restates the conditions).  mbnb_sparse_last_kernel() hands out name and variant in one buffer (name, NUL, variant,
+// NUL).  The variant of the "+dense" route's GEMM stays in libmbnb_hip's own record.
+thread_local char g_variant[64] = "";
+thread_local char g_kernel_out[128] = "";
+
+void set_variant(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+void set_variant(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_variant, sizeof(g_variant), fmt, ap);
+    va_end(ap);
+}
+// every launching entry point begins with this: a call whose launcher sets no variant reports "", never the previous call's
+void begin_call() { g_variant[0] = '\0'; }
+
+// a failed launch leaves the record as every failing call leaves it: the last successful call's name, no variant
 int launched(const char *what, int name) {
-    if (int rc = mbnb::launch_status(what)) return rc;
+    if (int rc = mbnb::launch_status(what)) {
+        g_variant[0] = '\0';
+        return rc;
+    }
     g_kernel = kSparseKernelNames[name];
     return MBNB_SPARSE_OK;
 }
@@ -626,6 +649,7 @@ int cr_dequant_launch(const int8_t *q, const float *rm, const float *cm, int64_t
     if (blocks > kMaxGrid) return fail(MBNB_SPARSE_ERR_UNSUPPORTED, "colrow_dequantize: %lld workgroups exceed one launch", (long long)blocks);
     if (C % 8 == 0 && aligned(q, 8) && aligned(cm, 16) && aligned(out, 16)) {
         hipLaunchKernelGGL((k_colrow_dequant<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, q, rm, cm, R, C, out, nchunk, write_through);
+        if (write_through && sizeof(T) == 2) set_variant("wt");      // the store that goes through to memory (the f32 form has none)
         return launched("colrow_dequantize", KN_CR_DQ8);
     }
     hipLaunchKernelGGL((k_colrow_dequant<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, q, rm, cm, R, C, out, nchunk, 0);
@@ -653,7 +677,10 @@ int cr_matmul(const T *X, int64_t M, int64_t K, const int8_t *W, const float *rm
         const int dt = std::is_same<T, f16_t>::value ? MBNB_F16 : MBNB_BF16;
         char *part = static_cast<char *>(ws) + wd_bytes;
         const int rc = mbnb_gemm_dense(X, wd, dt, bias, dt, out, M, N, K, K, part, ws_bytes - wd_bytes, 0, st);
-        if (rc != 0) return fail(rc, "colrow_matmul: mbnb_gemm_dense failed: %s", mbnb_last_error());
+        if (rc != 0) {
+            g_variant[0] = '\0';
+            return fail(rc, "colrow_matmul: mbnb_gemm_dense failed: %s", mbnb_last_error());
+        }
         g_kernel = kSparseKernelNames[KN_CR_DENSE];
         return MBNB_SPARSE_OK;
     }
@@ -678,7 +705,12 @@ extern "C" {
 
 int mbnb_sparse_abi_version(void) { return MBNB_SPARSE_ABI_VERSION; }
 const char *mbnb_sparse_last_error(void) { return mbnb::last_error(); }
-const char *mbnb_sparse_last_kernel(void) { return g_kernel; }
+const char *mbnb_sparse_last_kernel(void) {
+    const size_t n = strlen(g_kernel) + 1;
+    memcpy(g_kernel_out, g_kernel, n);
+    memcpy(g_kernel_out + n, g_variant, strlen(g_variant) + 1);
+    return g_kernel_out;
+}
 
 // --------------------------------------------------------------------------- col + row
 int64_t mbnb_colrow_quantize_workspace_bytes(int64_t R, int64_t C) {
@@ -688,6 +720,7 @@ int64_t mbnb_colrow_quantize_workspace_bytes(int64_t R, int64_t C) {
 
 int mbnb_colrow_quantize(const void *x, int dtype, int64_t R, int64_t C, int8_t *q, float *row_absmax, float *col_absmax, void *workspace,
                          int64_t workspace_bytes, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "colrow_quantize: unknown dtype %d", dtype);
     if (R < 0 || C < 0) return fail(MBNB_SPARSE_ERR_ARG, "colrow_quantize: negative size");
     if (C > 0 && R > kMaxElems / C) return fail(MBNB_SPARSE_ERR_SHAPE, "colrow_quantize: problem too large");
@@ -720,6 +753,7 @@ int mbnb_colrow_quantize(const void *x, int dtype, int64_t R, int64_t C, int8_t 
 
 int mbnb_colrow_dequantize(const int8_t *q, const float *row_scales, const float *col_scales, int64_t R, int64_t C, int dtype, void *out,
                            void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "colrow_dequantize: unknown dtype %d", dtype);
     if (R < 0 || C < 0) return fail(MBNB_SPARSE_ERR_ARG, "colrow_dequantize: negative size");
     if (C > 0 && R > kMaxElems / C) return fail(MBNB_SPARSE_ERR_SHAPE, "colrow_dequantize: problem too large");
@@ -746,6 +780,7 @@ int64_t mbnb_colrow_matmul_workspace_bytes(int64_t M, int64_t N, int64_t K, int 
 
 int mbnb_colrow_matmul(const void *X, int dtype, int64_t M, int64_t K, const int8_t *W, const float *row_scales, const float *col_scales, int64_t N,
                        const void *bias, void *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "colrow_matmul: unknown dtype %d", dtype);
     if (flags & ~(MBNB_SPARSE_PASS_ONLY | MBNB_SPARSE_FORCE_GENERIC)) return fail(MBNB_SPARSE_ERR_ARG, "colrow_matmul: unknown flags 0x%x", flags);
     if (flags & MBNB_SPARSE_PASS_ONLY) {     // the pass as the dense route runs it: write-through stores where the vector form applies
@@ -779,6 +814,7 @@ int mbnb_colrow_matmul(const void *X, int dtype, int64_t M, int64_t K, const int
 
 // --------------------------------------------------------------------------- dense -> COO
 int mbnb_coo_count(const void *x, int dtype, int64_t R, int64_t C, float threshold, int64_t *row_ptr, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "coo_count: unknown dtype %d", dtype);
     if (R < 0 || C < 0) return fail(MBNB_SPARSE_ERR_ARG, "coo_count: negative size");
     if (C > 0 && R > kMaxElems / C) return fail(MBNB_SPARSE_ERR_SHAPE, "coo_count: problem too large");
@@ -797,6 +833,7 @@ int mbnb_coo_count(const void *x, int dtype, int64_t R, int64_t C, float thresho
 
 int mbnb_coo_fill(const void *x, int dtype, int64_t R, int64_t C, float threshold, const int64_t *row_ptr, int64_t *row, int64_t *col, void *values,
                   int64_t nnz, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "coo_fill: unknown dtype %d", dtype);
     if (R < 0 || C < 0 || nnz < 0) return fail(MBNB_SPARSE_ERR_ARG, "coo_fill: negative size");
     if (C > 0 && (R > kMaxElems / C || nnz > R * C)) return fail(MBNB_SPARSE_ERR_SHAPE, "coo_fill: problem too large, or more entries than elements");
@@ -822,6 +859,7 @@ int mbnb_coo_fill(const void *x, int dtype, int64_t R, int64_t C, float threshol
 int64_t mbnb_coo_quantize_workspace_bytes(void) { return COO_QP * 4; }
 
 int mbnb_coo_quantize(const void *values, int dtype, int64_t nnz, int8_t *q, float *scale, void *workspace, int64_t workspace_bytes, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "coo_quantize: unknown dtype %d", dtype);
     if (nnz < 0) return fail(MBNB_SPARSE_ERR_ARG, "coo_quantize: negative size");
     if (nnz == 0) return fail(MBNB_SPARSE_ERR_SHAPE, "coo_quantize: nnz = 0: the maximum of no values is undefined");
@@ -838,6 +876,7 @@ int mbnb_coo_quantize(const void *values, int dtype, int64_t nnz, int8_t *q, flo
         using T = decltype(tag);
         hipLaunchKernelGGL(k_coo_absmax<T>, dim3((unsigned)nparts), dim3(256), 0, st, static_cast<const T *>(values), nnz, part);
         hipLaunchKernelGGL(k_coo_quantize<T>, dim3((unsigned)nparts), dim3(256), 0, st, static_cast<const T *>(values), nnz, part, nparts, q, scale);
+        set_variant("parts%d", nparts);
         return launched("coo_quantize", KN_COO_QUANT);
     });
 }
@@ -851,6 +890,7 @@ int64_t mbnb_spmm_coo_workspace_bytes(int64_t nnz, int64_t rows) {
 int mbnb_spmm_coo(const void *row, int row_bits, const void *col, int col_bits, const void *values, int value_kind, const float *scale, int64_t nnz,
                   const void *dense, int dtype, int64_t rows, int64_t cols, int64_t N, void *out, void *workspace, int64_t workspace_bytes, int flags,
                   void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_SPARSE_ERR_ARG, "spmm_coo: unknown dtype %d", dtype);
     if (flags & ~MBNB_SPARSE_FORCE_GENERIC) return fail(MBNB_SPARSE_ERR_ARG, "spmm_coo: unknown flags 0x%x", flags);
     if ((row_bits != 32 && row_bits != 64) || (col_bits != 32 && col_bits != 64)) return fail(MBNB_SPARSE_ERR_ARG, "spmm_coo: indices must be int32 or int64");
@@ -903,6 +943,7 @@ int mbnb_spmm_coo(const void *row, int row_bits, const void *col, int col_bits, 
         T *o = static_cast<T *>(out);
         if (vec) hipLaunchKernelGGL((k_spmm_csr<T, true>), dim3((unsigned)b_spmm), dim3(256), 0, st, flag, row_ptr, perm, col, col_bits, values, value_kind, scale, d, rows, cols, N, o, G, ntile);
         else hipLaunchKernelGGL((k_spmm_csr<T, false>), dim3((unsigned)b_spmm), dim3(256), 0, st, flag, row_ptr, perm, col, col_bits, values, value_kind, scale, d, rows, cols, N, o, G, ntile);
+        set_variant("G%d x%lld", G, (long long)ntile);
         return launched("spmm_coo", vec ? (general ? KN_SPMM8_GEN : KN_SPMM8) : (general ? KN_SPMM1_GEN : KN_SPMM1));
     });
 }

@@ -3,6 +3,8 @@
 //   the weight gradient               dW = dY^T . X   (a contraction over the token dimension M)
 // The MFMA work is libmbnb_hip's public mbnb_gemm_dense with the library's own plan (slices = 0); this file holds the passes that
 // feed it and the generic kernels for what it does not take.  Its own last-error and kernel-name records (mbnb_train_last_*).
+#include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 #include "../../include/mbnb_train.h"
@@ -226,14 +228,35 @@ const char *const kTrainKernelNames[] = {"switchback_dq", "switchback_dq+dense",
 
 thread_local const char *g_kernel = "";
 
+// The variant of the last call: which kernel forms ran behind the name, as words joined by blanks ("dq8x4 bias8", "dy1 x8"; tests/
+// switchback_cases.py restates the conditions).  mbnb_train_last_kernel() hands out name and variant in one buffer (name, NUL, variant, NUL).
+// The variant of a "+dense" route's GEMM stays in libmbnb_hip's own record.
+thread_local char g_variant[64] = "";
+thread_local char g_kernel_out[128] = "";
+
+void set_variant(const char *word) { snprintf(g_variant, sizeof(g_variant), "%s", word); }
+void add_variant(const char *word) {
+    const size_t n = strlen(g_variant);
+    snprintf(g_variant + n, sizeof(g_variant) - n, n ? " %s" : "%s", word);
+}
+// every launching entry point begins with this: a call whose launcher sets no variant reports "", never the previous call's
+void begin_call() { g_variant[0] = '\0'; }
+
+// a failed launch leaves the record as every failing call leaves it: the last successful call's name, no variant
 int launched(const char *what, int name) {
-    if (int rc = mbnb::launch_status(what)) return rc;
+    if (int rc = mbnb::launch_status(what)) {
+        g_variant[0] = '\0';
+        return rc;
+    }
     g_kernel = kTrainKernelNames[name];
     return MBNB_TRAIN_OK;
 }
 
 int from_gemm(int rc, const char *what) {
-    if (rc != 0) return fail(rc, "%s: mbnb_gemm_dense failed: %s", what, mbnb_last_error());
+    if (rc != 0) {
+        g_variant[0] = '\0';
+        return fail(rc, "%s: mbnb_gemm_dense failed: %s", what, mbnb_last_error());
+    }
     return MBNB_TRAIN_OK;
 }
 
@@ -262,15 +285,18 @@ int sb_pass(const int8_t *W, const float *scales, int64_t N, int64_t K, T *out, 
             const unsigned gx = (unsigned)((K / 8 + 255) / 256);
             if (N * K <= ((int64_t)1 << 25) && (N + 3) / 4 <= 65535) {
                 hipLaunchKernelGGL((k_switchback_dq8<T, 4>), dim3(gx, (unsigned)((N + 3) / 4)), dim3(256), 0, st, q, scales, N, K, out, write_through);
+                set_variant("dq8x4");
                 return 0;
             }
             if (N <= 65535) {
                 hipLaunchKernelGGL((k_switchback_dq8<T, 1>), dim3(gx, (unsigned)N), dim3(256), 0, st, q, scales, N, K, out, write_through);
+                set_variant("dq8x1");
                 return 0;
             }
         }
     }
     hipLaunchKernelGGL(k_switchback_dq1<T>, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, st, W, scales, N, K, out);   // N K <= kMaxElems
+    set_variant("dq1");
     return 0;
 }
 
@@ -296,11 +322,14 @@ int sb_forward(const T *X, int64_t M, int64_t K, const int8_t *W, const float *s
         char *part = static_cast<char *>(ws) + wd_bytes;
         if (int rc = from_gemm(mbnb_gemm_dense(X, wd, dt, nullptr, dt, out, M, N, K, K, part, ws_bytes - wd_bytes, 0, st), "switchback_forward"))
             return rc;
-        if (bias) {
-            if (N % 8 == 0 && aligned(bias, 16))
-                hipLaunchKernelGGL((k_bias_add<T, true>), dim3((unsigned)((M * N / 8 + 255) / 256)), dim3(256), 0, st, out, bias, M, N);
-            else
-                hipLaunchKernelGGL((k_bias_add<T, false>), dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st, out, bias, M, N);
+        if (!bias) {
+            add_variant("nobias");
+        } else if (N % 8 == 0 && aligned(bias, 16)) {
+            hipLaunchKernelGGL((k_bias_add<T, true>), dim3((unsigned)((M * N / 8 + 255) / 256)), dim3(256), 0, st, out, bias, M, N);
+            add_variant("bias8");
+        } else {
+            hipLaunchKernelGGL((k_bias_add<T, false>), dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st, out, bias, M, N);
+            add_variant("bias1");
         }
         return launched("switchback_forward(bias)", KN_SB_DENSE);
     }
@@ -327,13 +356,15 @@ int64_t gw_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype) {
     return round256(N * Mp * 2) + round256(K * Mp * 2) + mbnb_gemm_dense_workspace_bytes(N, K, Mp);
 }
 
-// A [M, C] -> out [C, Mp]; C / 256 <= 65535 (checked by the callers)
-void transpose_pad(const void *A, int64_t M, int64_t C, int64_t Mp, void *out, int write_through, hipStream_t st) {
+// A [M, C] -> out [C, Mp]; C / 256 <= 65535 (checked by the callers).  True where the 16-byte loads ran.
+bool transpose_pad(const void *A, int64_t M, int64_t C, int64_t Mp, void *out, int write_through, hipStream_t st) {
     const dim3 grid((unsigned)(Mp / 64), (unsigned)((C + 255) / 256));
     const uint16_t *a = static_cast<const uint16_t *>(A);
     uint16_t *o = static_cast<uint16_t *>(out);
-    if (C % 8 == 0 && aligned(A, 16)) hipLaunchKernelGGL(k_transpose_pad<true>, grid, dim3(256), 0, st, a, M, C, Mp, o, write_through);
+    const bool vec = C % 8 == 0 && aligned(A, 16);
+    if (vec) hipLaunchKernelGGL(k_transpose_pad<true>, grid, dim3(256), 0, st, a, M, C, Mp, o, write_through);
     else hipLaunchKernelGGL(k_transpose_pad<false>, grid, dim3(256), 0, st, a, M, C, Mp, o, write_through);
+    return vec;
 }
 
 template <typename T>
@@ -351,7 +382,8 @@ int gw_dispatch(const void *dY, const void *X, int64_t M, int64_t N, int64_t K, 
         if (!is16(dtype) || 256 * Mp * 2 >= ((int64_t)1 << 31) || (K + 255) / 256 > 65535 || !aligned(dW, 16))
             return fail(MBNB_TRAIN_ERR_UNSUPPORTED, "linear_grad_weight: the transposing pass alone needs a 16-bit dtype, a 16-byte aligned "
                                                     "output and sizes within one launch");
-        transpose_pad(X, M, K, Mp, dW, 0, st);
+        if (transpose_pad(X, M, K, Mp, dW, 0, st)) set_variant("x8");
+        else set_variant("x1");
         return launched("linear_grad_weight(pass)", KN_GW_T);
     }
     const int64_t yt_bytes = round256(N * Mp * 2), xt_bytes = round256(K * Mp * 2);
@@ -359,8 +391,10 @@ int gw_dispatch(const void *dY, const void *X, int64_t M, int64_t N, int64_t K, 
                        ws_bytes >= yt_bytes + xt_bytes && aligned(dW, 16);
     if (dense) {
         char *wsb = static_cast<char *>(ws);
-        transpose_pad(dY, M, N, Mp, wsb, 1, st);
-        transpose_pad(X, M, K, Mp, wsb + yt_bytes, 1, st);
+        if (transpose_pad(dY, M, N, Mp, wsb, 1, st)) set_variant("dy8");
+        else set_variant("dy1");
+        if (transpose_pad(X, M, K, Mp, wsb + yt_bytes, 1, st)) add_variant("x8");
+        else add_variant("x1");
         if (int rc = launched("linear_grad_weight(transpose)", KN_GW_T)) return rc;
         if (int rc = from_gemm(mbnb_gemm_dense(wsb, wsb + yt_bytes, dtype, nullptr, dtype, dW, N, K, Mp, Mp, wsb + yt_bytes + xt_bytes,
                                                ws_bytes - yt_bytes - xt_bytes, 0, st),
@@ -383,7 +417,12 @@ extern "C" {
 
 int mbnb_train_abi_version(void) { return MBNB_TRAIN_ABI_VERSION; }
 const char *mbnb_train_last_error(void) { return mbnb::last_error(); }
-const char *mbnb_train_last_kernel(void) { return g_kernel; }
+const char *mbnb_train_last_kernel(void) {
+    const size_t n = strlen(g_kernel) + 1;
+    memcpy(g_kernel_out, g_kernel, n);
+    memcpy(g_kernel_out + n, g_variant, strlen(g_variant) + 1);
+    return g_kernel_out;
+}
 int64_t mbnb_train_padded_rows(int64_t M) { return M < 0 ? 0 : padded_rows(M); }
 
 int64_t mbnb_switchback_forward_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype) {
@@ -393,6 +432,7 @@ int64_t mbnb_switchback_forward_workspace_bytes(int64_t M, int64_t N, int64_t K,
 
 int mbnb_switchback_forward(const void *X, int dtype, int64_t M, int64_t K, const int8_t *W, const float *scales, int64_t N, const void *bias,
                             void *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_TRAIN_ERR_ARG, "switchback_forward: unknown dtype %d", dtype);
     if (flags & ~(MBNB_TRAIN_PASS_ONLY | MBNB_TRAIN_FORCE_GENERIC)) return fail(MBNB_TRAIN_ERR_ARG, "switchback_forward: unknown flags 0x%x", flags);
     const bool pass = flags & MBNB_TRAIN_PASS_ONLY;
@@ -427,6 +467,7 @@ int64_t mbnb_linear_grad_weight_workspace_bytes(int64_t M, int64_t N, int64_t K,
 
 int mbnb_linear_grad_weight(const void *dY, const void *X, int64_t M, int64_t N, int64_t K, int dtype, void *dW, void *workspace,
                             int64_t workspace_bytes, int flags, void *stream) {
+    begin_call();
     if (!dtype_ok(dtype)) return fail(MBNB_TRAIN_ERR_ARG, "linear_grad_weight: unknown dtype %d", dtype);
     if (flags & ~(MBNB_TRAIN_PASS_ONLY | MBNB_TRAIN_FORCE_GENERIC)) return fail(MBNB_TRAIN_ERR_ARG, "linear_grad_weight: unknown flags 0x%x", flags);
     const bool pass = flags & MBNB_TRAIN_PASS_ONLY;

@@ -1,5 +1,6 @@
 """
-Guarded allocations for the quantise / dequantise tests.
+Guarded allocations for the GPU tests that run a kernel form inside guard bands: the quantise / dequantise forms (tests/quant_cases.py)
+and every case of the train and sparse libraries' tables that launches no GEMM (tests/forms.py).
 
 ``guarded_alloc`` replaces the name ``torch`` inside ``mps_bitsandbytes_amd.functional`` with a proxy that forwards every attribute
 to torch except ``empty``: the request is carved out of a larger uint8 buffer with a guard band of GUARD bytes on each side, every

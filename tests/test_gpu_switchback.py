@@ -15,9 +15,11 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _train_native, synthetic
 from mps_bitsandbytes_amd import functional as F
 from mps_bitsandbytes_amd.optim import AdamW8bit
-from tests import switchback_cases
+from tests import forms, guard, switchback_cases
+from tests.forms import memo as _memo
 from tests.elementwise import UNIT, assert_bound_elementwise, assert_linear_elementwise
 from tests.goldenio import DT, HERE, from_bits, rel_fro
+from tests.guard import guarded_alloc  # noqa: F401  (the fixture, by name: it replaces poisoned_alloc's proxy in the tests that ask for it)
 from tests.poison import poisoned_alloc  # noqa: F401  (the fixture, by name: every torch.empty of functional.py comes back 0xFF)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_alloc")]
@@ -35,68 +37,134 @@ def _bits(t):
     return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32) if t.dtype == torch.float32 else t
 
 
+def _nan_bits(t):
+    """_bits with every NaN as the dtype's default NaN: the contract says where a NaN is, not which one."""
+    t = t.detach().cpu()
+    return _bits(torch.where(torch.isnan(t), torch.full_like(t, float("nan")), t))
+
+
 def _weights(N, K, seed):
     W = synthetic.normal((N, K), torch.float32, seed=seed, std=0.02)
     q, s = F.quantize_rowwise(W.to(DEV))
     return q, s
 
 
-def _shifted(t, view):
-    """t itself, or a copy 2 bytes off 16-byte alignment (view == "misaligned")."""
-    if view != "misaligned":
-        return t
-    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=t.device)
-    out = buf[1:1 + t.numel()].view(t.shape)
-    out.copy_(t)
-    return out
-
-
 # ----------------------------------------------------------------------------- every case of the table
-@pytest.mark.parametrize("case", switchback_cases.CASES, ids=switchback_cases.case_id)
-def test_case_elementwise(case):
+_SENTINEL = {}
+
+
+def _sentinel(case):
+    """A call of the library's other entry point, on a generic kernel that sets no variant: the case's own name and variant cannot be
+    left over from the call before."""
+    if not _SENTINEL:
+        _SENTINEL["x"] = torch.ones(3, 8, device=DEV)
+        _SENTINEL["q"] = torch.ones(5, 8, dtype=torch.int8, device=DEV)
+        _SENTINEL["s"] = torch.ones(5, device=DEV)
+    if case["op"] in ("forward", "dequant"):
+        F._linear_grad_weight(_SENTINEL["x"], _SENTINEL["x"])
+        name = "grad_w_generic"
+    else:
+        F._switchback_forward(_SENTINEL["x"], _SENTINEL["q"], _SENTINEL["s"])
+        name = "switchback_generic"
+    assert _train_native.last_kernel() == name
+    assert _train_native.last_variant() == "", "a call whose launcher sets no variant reports the previous call's"
+
+
+def _Run(case, proxy=None, fill=None):
+    return forms.Run(switchback_cases, _train_native, _sentinel, case, proxy, fill)
+
+
+def _case_weights(case, N, K, seed):
+    """(codes, scales) on the device; the larger weights of the FORMS cases are drawn on the device."""
+    if N * K <= 1 << 23 or not any(case is c for c in switchback_cases.FORMS):
+        return _weights(N, K, seed)
+    return F.quantize_rowwise(synthetic.normal_device((N, K), torch.float32, seed=seed, std=0.02, device=DEV))
+
+
+def _run_case(case, proxy=None, fill=None):
     T = DT[case["dt"]]
     K, seed = case["K"], 1500 + case["K"] % 97
     flags = _train_native.FORCE_GENERIC if case.get("generic") else 0
     lead = tuple(case["lead"]) if "lead" in case else (case.get("M", 0),)
+    run = _Run(case, proxy, fill)
+    nonfinite = case.get("special") == "nonfinite"
     if case["op"] == "dequant":
-        q, s = _weights(case["N"], K, seed)
-        wd = F._switchback_dequant(q, s, T)
-        assert _train_native.last_kernel() == case["kernel"]
-        assert torch.equal(_bits(wd), _bits(_wd_rule(q.cpu(), s.cpu(), T)))
+        q, s = _case_weights(case, case["N"], K, seed)
+        if nonfinite:
+            s[3], s[5], s[7] = float("nan"), float("inf"), float("-inf")
+            q[5, 2] = 0          # 0 * Inf
+        want = _memo(("wd", run.id), lambda: _nan_bits(_wd_rule(q.cpu(), s.cpu(), T)))
+        run.begin()
+        wd = F._switchback_dequant(run.put("w", q), s, T)
+        run.end()
+        assert torch.equal(_nan_bits(wd), want)
+        if nonfinite:
+            assert bool(torch.isnan(wd[3]).all()) and bool(torch.isnan(wd[5, 2])) and bool(torch.isinf(wd[7, q[7] != 0]).all())
         return
     if case["op"] == "transpose":
         M = case["M"]
         x = synthetic.normal((M, K), T, seed=seed).to(DEV)
+        run.begin()
+        x = run.put("x", x)
         xt = F._transpose_pad(x)
-        assert _train_native.last_kernel() == case["kernel"]
+        run.end()
         Mp = _train_native.padded_rows(M)
-        assert xt.shape == (K, Mp)
+        assert Mp == switchback_cases.padded_rows(M) and xt.shape == (K, Mp)
         assert torch.equal(_bits(xt[:, :M]), _bits(x.t()))
         assert not bool(_bits(xt[:, M:]).any()), "pad columns must be written as zeros"
         return
     if case["op"] == "forward":
         N = case["N"]
-        q, s = _weights(N, K, seed)
-        x = _shifted(synthetic.normal(lead + (K,), T, seed=seed + 1, std=1.0).to(DEV), case.get("view"))
+        q, s = _case_weights(case, N, K, seed)
+        x = synthetic.normal(lead + (K,), T, seed=seed + 1, std=1.0).to(DEV)
         b = synthetic.normal((N,), T, seed=seed + 2).to(DEV) if case.get("bias") else None
+        if nonfinite:
+            s[3], s[5], s[7] = float("nan"), float("inf"), float("-inf")
+            x[2, 9], x[4, 11], x[6, 13] = float("nan"), float("inf"), float("-inf")
+        wd = _memo(("fwd", run.id), lambda: _wd_rule(q.cpu(), s.cpu(), T))
+        run.begin()
+        x, q, b = run.put("x", x), run.put("w", q), run.put("bias", b)
         y0 = F._switchback_forward(x, q, s, None, flags)
-        assert _train_native.last_kernel() == case["kernel"]
+        if b is None:
+            run.end()
+        else:           # the bias-free call of a case with a bias: its own name and variant, by the restated conditions
+            got = (_train_native.last_kernel(), _train_native.last_variant())
+            assert got == switchback_cases.model(dict(case, bias=False)), f"{run.id} without its bias: the library reports {got}"
         assert y0.shape == lead + (N,) and y0.dtype == T
-        wd = _wd_rule(q.cpu(), s.cpu(), T)
         assert_linear_elementwise(y0, x.cpu(), wd, None, T, T, case["kernel"])
         if b is not None:
+            _sentinel(case)             # so that the second call's name cannot be the first one's
+            if proxy is not None:       # the second call's allocations: the same plan again
+                proxy.plan = run.plan()
             y = F._switchback_forward(x, q, s, b, flags)
-            assert _train_native.last_kernel() == case["kernel"]
-            assert torch.equal(_bits(y), _bits(y0 + b)), "the bias is one more rounding of the bias-free product"
+            run.end()
+            assert torch.equal(_nan_bits(y), _nan_bits(y0 + b)), "the bias is one more rounding of the bias-free product"
         return
     # grad_w: dW = dY^T . X, checked as y = X' . Wd'^T with X' = dY^T [N, M], Wd' = X^T [K, M]
     N = case["N"]
-    dy = _shifted(synthetic.normal(lead + (N,), T, seed=seed + 3).to(DEV), case.get("view"))
-    x = _shifted(synthetic.normal(lead + (K,), T, seed=seed + 4).to(DEV), case.get("view"))
+    dy = synthetic.normal(lead + (N,), T, seed=seed + 3).to(DEV)
+    x = synthetic.normal(lead + (K,), T, seed=seed + 4).to(DEV)
+    run.begin()
+    dy, x = run.put("dy", dy), run.put("x", x)
     dW = F._linear_grad_weight(dy, x, flags)
-    assert _train_native.last_kernel() == case["kernel"]
+    run.end()
     assert dW.shape == (N, K) and dW.dtype == T
     assert_linear_elementwise(dW, dy.reshape(-1, N).t().cpu(), x.reshape(-1, K).t().cpu(), None, T, T, case["kernel"])
+
+
+@pytest.mark.parametrize("case", [c for c in switchback_cases.CASES if not switchback_cases.needs_plan(c)], ids=switchback_cases.case_id)
+def test_case_elementwise(case):
+    _run_case(case)
+
+
+# every case that launches no GEMM again, inside guard bands and under two fills (tests/guard.py): an element the kernel never wrote holds
+# the fill and cannot equal the reference under both; a store outside a buffer changes a band.  The cases that place one of functional.py's
+# own allocations off its alignment run here only.
+@pytest.mark.parametrize("fill", guard.FILLS, ids=lambda f: f"fill{f:02X}")
+@pytest.mark.parametrize("case", [c for c in switchback_cases.CASES if not switchback_cases.launches_gemm(c)], ids=switchback_cases.case_id)
+def test_case_guarded(case, fill, guarded_alloc):
+    _run_case(case, guarded_alloc, fill)
+    assert guarded_alloc.allocs, "nothing went through the guarded proxy"
 
 
 def test_grad_weight_of_no_tokens_is_zero():

@@ -17,7 +17,7 @@ import torch
 import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _native, _optim_native, _sparse_native, _train_native
 from mps_bitsandbytes_amd import functional as F
-from tests import int8_decomp_cases
+from tests import forms, int8_decomp_cases
 from tests import int8_decomp_emul as emul
 from tests.goldenio import DT, HERE, from_bits
 
@@ -174,12 +174,132 @@ def test_every_reported_kernel_name_is_the_kernel_of_a_case():
     assert set(names) == expected, (sorted(set(names) - expected), sorted(expected - set(names)))
 
 
+# ----------------------------------------------------------------------------- forms behind the names: variants, limits, alignment, dtypes
+_code = forms.code
+
+
+def reported_variants(src):
+    """Regexes of the variant strings the source can report: every set_variant("...") call, %d / %lld as a number."""
+    fmts = re.findall(r'\bset_variant\("([^"]*)"', _code(src))
+    return {"".join(r"\d+" if part in ("%d", "%lld") else re.escape(part) for part in re.split(r"(%lld|%d)", f)) for f in fmts}
+
+
+def uncovered_variants(src, cases):
+    """(patterns no case takes, variants of cases that no pattern gives)."""
+    pats, have = reported_variants(src), {c["variant"] for c in cases}
+    return (sorted(p for p in pats if not any(re.fullmatch(p, v) for v in have)),
+            sorted(v for v in have if v and not any(re.fullmatch(p, v) for p in pats)))
+
+
+MARKER = "enum { KN_CR_Q8"       # the host side of sparse_kernels.hip begins here (tests/forms.py)
+
+
+def limit_counts(src):
+    return forms.limit_counts(src, MARKER)
+
+
+def alignment_tests(src):
+    return forms.alignment_tests(src, MARKER)
+
+
+def test_every_variant_the_source_reports_has_a_case_and_no_case_names_another():
+    src = open(SRC).read()
+    assert reported_variants(src) == {"wt", r"parts\d+", r"G\d+\ x\d+"}
+    assert uncovered_variants(src, int8_decomp_cases.CASES) == ([], [])
+    # every launching entry point empties the variant first
+    entries = re.findall(r"^int (mbnb_\w+)\([^{]*\{\n(.*)\n", src, flags=re.M)
+    assert len(entries) == 7 and all(first.strip() == "begin_call();" for _, first in entries), entries
+
+
+def test_every_case_takes_the_name_and_the_variant_the_launchers_conditions_give():
+    for c in int8_decomp_cases.CASES:
+        assert int8_decomp_cases.model(c) == (c["kernel"], c["variant"]), (int8_decomp_cases.case_id(c), int8_decomp_cases.model(c))
+
+
+def test_every_threshold_has_a_case_on_each_side():
+    rows = [t[0] for t in int8_decomp_cases.THRESHOLDS]
+    assert len(rows) == len(set(rows))
+    for what, ops, first, second in int8_decomp_cases.THRESHOLDS:
+        cs = [(c, int8_decomp_cases.derived(c)) for c in int8_decomp_cases.CASES if c["op"] in ops]
+        assert any(first(c, d) for c, d in cs), f"{what}: no case on the first side"
+        assert any(second(c, d) for c, d in cs), f"{what}: no case on the second side"
+
+
+def unclaimed_limits(src):
+    """Literals and tile constants of the source that LIMIT_COUNTS / LIMIT_CLAIMS do not know (or know with another count)."""
+    m = int8_decomp_cases
+    counts = limit_counts(src)
+    consts = set(re.findall(r"constexpr int (\w+) = \d+;", _code(src)))
+    return sorted(k for k in set(counts) | set(m.LIMIT_COUNTS) if counts.get(k) != m.LIMIT_COUNTS.get(k)) + sorted(consts ^ set(m.TILE_CONSTANTS))
+
+
+def test_every_limit_of_the_launchers_is_claimed_by_a_threshold_or_listed_as_having_no_case():
+    m = int8_decomp_cases
+    assert unclaimed_limits(open(SRC).read()) == []
+    rows = {t[0] for t in m.THRESHOLDS} | {m._CSR}
+    assert set(m.LIMIT_CLAIMS) == set(m.LIMIT_COUNTS) | set(m.TILE_CONSTANTS)
+    for lit, claim in m.LIMIT_CLAIMS.items():
+        if isinstance(claim, tuple):
+            assert claim[0] == "no case" and claim[1], lit
+        else:
+            assert set([claim] if isinstance(claim, str) else claim) <= rows, lit
+    for lit in ("1 << 31", "1 << 40", "kMaxGrid", "kMaxElems"):
+        assert m.LIMIT_CLAIMS[lit][0] == "no case"
+    assert set(m.CSR_ROW_LENGTHS) >= {0, 1, 2, 3, 5, m.COO_SORT_LDS - 1, m.COO_SORT_LDS, m.COO_SORT_LDS + 1} and \
+        [-(-r // m.SCAN_THREADS) for r in m.CSR_ROW_COUNTS] == [1, 2, 5]
+
+
+def _pair(op, operand):
+    return forms.pair(int8_decomp_cases.CASES, op, operand)
+
+
+def test_every_pointer_a_launcher_tests_has_a_pair_of_cases_that_differ_by_its_offset_alone():
+    m = int8_decomp_cases
+    assert alignment_tests(open(SRC).read()) == set(m.OPERAND_ALIGNMENT_TESTED) | m.ALIGNMENT_REQUIRED
+    for key, (op, operand) in m.OPERAND_ALIGNMENT_TESTED.items():
+        pairs = _pair(op, operand)
+        assert pairs and all((c["kernel"], c["variant"]) != (b["kernel"], b["variant"]) for c, b in pairs), key
+    for op, operand in m.OPERAND_ALIGNMENT_FREE:
+        pairs = _pair(op, operand)
+        assert pairs and all((c["kernel"], c["variant"]) == (b["kernel"], b["variant"]) for c, b in pairs), (op, operand)
+
+
+def test_every_form_has_a_case_for_each_dtype_it_is_instantiated_for():
+    m = int8_decomp_cases
+    for (name, variant), dts in m.INSTANTIATED.items():
+        if name.startswith("spmm int8"):
+            have = {c["dt"] for c in m.CASES if c["op"] == "spmm" and c["values"] == name.split()[1]}
+        else:
+            have = {c["dt"] for c in m.CASES if c["kernel"] == name and (variant is None or c["variant"] == variant or c["variant"].startswith(variant + " "))}
+        assert set(dts) <= have, (name, variant, sorted(set(dts) - have))
+    assert {c["kernel"] for c in m.CASES} <= {k[0] for k in m.INSTANTIATED}
+    src = _code(open(SRC).read())
+    assert "with_dtype" in src and not re.search(r"hipLaunchKernelGGL\(\(?k_\w+<(?:f16_t|bf16_t|float)\b", src), "every kernel template is instantiated through with_dtype: all three dtypes"
+
+
+def test_the_closure_fails_on_a_variant_a_limit_or_a_pointer_test_without_a_case():
+    """Three scratch edits of the source, each caught by its check."""
+    m = int8_decomp_cases
+    src = open(SRC).read()
+    a = src.replace('set_variant("parts%d", nparts);', 'if (nparts == 3) set_variant("three");\n        else set_variant("parts%d", nparts);')
+    assert a != src and uncovered_variants(a, m.CASES) == (["three"], [])
+    b = src.replace("const bool vec = vec_shape && aligned(dense, 16)", "const bool vec = vec_shape && N >= 24 && aligned(dense, 16)")
+    assert b != src and unclaimed_limits(b) == ["24"]
+    c = src.replace("const bool vec = vec_shape && aligned(dense, 16)", "const bool vec = vec_shape && aligned(values, 16) && aligned(dense, 16)")
+    assert c != src and alignment_tests(c) - set(m.OPERAND_ALIGNMENT_TESTED) - m.ALIGNMENT_REQUIRED == {("spmm_coo", "values", 16)}
+
+
 def test_cases_are_well_formed():
     ids = [int8_decomp_cases.case_id(c) for c in int8_decomp_cases.CASES]
     assert len(ids) == len(set(ids))
     for c in int8_decomp_cases.CASES:
         assert c["op"] in ("quantize", "dequant", "matmul", "count", "from_dense", "quantize_coo", "spmm"), c
         assert c["dt"] in ("f16", "bf16", "f32"), c
+        assert isinstance(c["variant"], str) and set(c) <= {"op", "kernel", "variant", "R", "C", "M", "N", "K", "lead", "dt", "bias", "generic", "view", "route",
+                                                            "threshold", "density", "n", "rows", "cols", "index", "values", "off", "special"}, c
+        for operand, off in c.get("off", {}).items():
+            assert 0 < off < 16 and operand in {"quantize": "x q rs cs", "dequant": "q rm cm out", "matmul": "x w rm cm bias out ws",
+                                                "spmm": "row col values dense out"}[c["op"]].split(), c
         if c["op"] == "spmm":
             assert c["index"] in ("sorted", "permuted", "int32", "duplicates") and c["values"] in ("T", "int8", "int8_entry"), c
             assert c["kernel"].endswith("_general") == bool(c.get("generic")), c

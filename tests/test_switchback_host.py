@@ -14,7 +14,7 @@ from torch import nn
 import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _train_native
 from mps_bitsandbytes_amd import functional as F
-from tests import switchback_cases
+from tests import forms, switchback_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "mps_bitsandbytes_amd", "csrc", "train_kernels.hip")
@@ -122,11 +122,124 @@ def test_every_reported_kernel_name_is_the_kernel_of_a_case():
     assert set(names) == expected, (sorted(set(names) - expected), sorted(expected - set(names)))
 
 
+# ----------------------------------------------------------------------------- forms behind the names: variants, limits, alignment, dtypes
+_code = forms.code
+MARKER = "enum { KN_SB_DQ"       # the host side of train_kernels.hip begins here (tests/forms.py)
+
+
+def reported_words(src):
+    """Every word a variant can hold: the literals of set_variant("...") and add_variant("...")."""
+    return set(re.findall(r'\b(?:set|add)_variant\("([^"]*)"\)', _code(src)))
+
+
+def uncovered_words(src, cases):
+    """(words no case's variant holds, words of cases that the source never reports)."""
+    words, have = reported_words(src), {w for c in cases for w in c["variant"].split()}
+    return sorted(words - have), sorted(have - words)
+
+
+def limit_counts(src):
+    return forms.limit_counts(src, MARKER)
+
+
+def unclaimed_limits(src):
+    counts = limit_counts(src)
+    return sorted(k for k in set(counts) | set(switchback_cases.LIMIT_COUNTS) if counts.get(k) != switchback_cases.LIMIT_COUNTS.get(k))
+
+
+def alignment_tests(src):
+    return forms.alignment_tests(src, MARKER)
+
+
+def test_every_variant_word_the_source_reports_has_a_case_and_no_case_names_another():
+    src = open(SRC).read()
+    assert reported_words(src) == {"dq8x4", "dq8x1", "dq1", "bias8", "bias1", "nobias", "dy8", "dy1", "x8", "x1"}
+    assert uncovered_words(src, switchback_cases.CASES) == ([], [])
+    have = {(c["kernel"], c["variant"]) for c in switchback_cases.CASES}
+    # the words as the launchers join them: the three Wd kernels alone, each bias word behind a vector Wd pass, the four pairs of transposes
+    assert {("switchback_dq", w) for w in ("dq8x4", "dq8x1", "dq1")} <= have
+    assert {("switchback_dq+dense", "dq8x4 " + b) for b in ("bias8", "bias1", "nobias")} | {("switchback_dq+dense", "dq8x1 bias8")} <= have
+    assert {("grad_w_t+dense", f"{a} {b}") for a in ("dy8", "dy1") for b in ("x8", "x1")} | {("grad_w_t", "x8"), ("grad_w_t", "x1")} <= have
+    assert all(c["variant"] == "" for c in switchback_cases.CASES if c["kernel"].endswith("generic"))
+    entries = re.findall(r"^int (mbnb_\w+)\([^{]*\{\n(.*)\n", src, flags=re.M)
+    assert len(entries) == 2 and all(first.strip() == "begin_call();" for _, first in entries), entries
+
+
+def test_every_case_takes_the_name_and_the_variant_the_launchers_conditions_give():
+    for c in switchback_cases.CASES:
+        assert switchback_cases.model(c) == (c["kernel"], c["variant"]), (switchback_cases.case_id(c), switchback_cases.model(c))
+    lib = _train_native.lib()
+    for M in (0, 1, 63, 64, 65, 127, 128, 129, 4095, 4097):
+        assert switchback_cases.padded_rows(M) == lib.mbnb_train_padded_rows(M)
+    # the restated shape conditions against the library's own workspace queries (0 where the dense route does not apply)
+    for c in switchback_cases.CASES:
+        if c["op"] in ("forward", "grad_w") and "off" not in c and "view" not in c and not c.get("generic"):
+            q = lib.mbnb_switchback_forward_workspace_bytes if c["op"] == "forward" else lib.mbnb_linear_grad_weight_workspace_bytes
+            code = {"f16": 0, "bf16": 1, "f32": 2}[c["dt"]]
+            assert (q(switchback_cases.rows_of(c), c["N"], c["K"], code) > 0) == c["kernel"].endswith("+dense"), switchback_cases.case_id(c)
+
+
+def test_every_threshold_has_a_case_on_each_side():
+    rows = [t[0] + str(t[1]) for t in switchback_cases.THRESHOLDS]
+    assert len(rows) == len(set(rows))
+    for what, ops, first, second in switchback_cases.THRESHOLDS:
+        cs = [(c, switchback_cases.derived(c)) for c in switchback_cases.CASES if c["op"] in ops]
+        assert any(first(c, d) for c, d in cs), f"{what} {ops}: no case on the first side"
+        assert any(second(c, d) for c, d in cs), f"{what} {ops}: no case on the second side"
+
+
+def test_every_limit_of_the_launchers_is_claimed_by_a_threshold_or_listed_as_having_no_case():
+    m = switchback_cases
+    assert unclaimed_limits(open(SRC).read()) == []
+    rows = {t[0] for t in m.THRESHOLDS}
+    assert set(m.LIMIT_CLAIMS) == set(m.LIMIT_COUNTS)
+    for lit, claim in m.LIMIT_CLAIMS.items():
+        for one in (claim if isinstance(claim, list) else [claim]):
+            assert one in rows or (isinstance(one, tuple) and one[0] == "no case" and one[1]), (lit, one)
+    for lit in ("1 << 31", "1 << 40", "0x7FFFFFFF", "kMaxElems"):
+        assert m.LIMIT_CLAIMS[lit][0] == "no case"
+
+
+def _pair(op, operand):
+    return forms.pair(switchback_cases.CASES, op, operand)
+
+
+def test_every_pointer_a_launcher_tests_has_a_pair_of_cases_that_differ_by_its_offset_alone():
+    m = switchback_cases
+    assert alignment_tests(open(SRC).read()) == set(m.OPERAND_ALIGNMENT_TESTED)
+    for key, (op, operand) in list(m.OPERAND_ALIGNMENT_TESTED.items()) + [(k, k) for k in m.OPERAND_ALIGNMENT_ALSO]:
+        pairs = _pair(op, operand)
+        assert pairs and all((c["kernel"], c["variant"]) != (b["kernel"], b["variant"]) for c, b in pairs), key
+
+
+def test_every_form_has_a_case_for_each_dtype_it_is_instantiated_for():
+    m = switchback_cases
+    for (name, variant), dts in m.INSTANTIATED.items():
+        have = {c["dt"] for c in m.CASES if (c["kernel"], c["variant"]) == (name, variant)}
+        assert set(dts) <= have, (name, variant, sorted(set(dts) - have))
+    assert {c["kernel"] for c in m.CASES} <= {k[0] for k in m.INSTANTIATED}
+
+
+def test_the_closure_fails_on_a_variant_a_limit_or_a_pointer_test_without_a_case():
+    """Three scratch edits of the source, each caught by its check."""
+    m = switchback_cases
+    src = open(SRC).read()
+    a = src.replace('add_variant("nobias");', 'if (N > 7) add_variant("nobias");\n            else add_variant("tiny");')
+    assert a != src and uncovered_words(a, m.CASES) == (["tiny"], [])
+    b = src.replace("if (N <= 65535) {", "if (N <= 65535 && K >= 24) {")
+    assert b != src and unclaimed_limits(b) == ["24"]
+    c = src.replace("ws_bytes >= yt_bytes + xt_bytes && aligned(dW, 16);", "ws_bytes >= yt_bytes + xt_bytes && aligned(dW, 16) && aligned(X, 16);")
+    assert c != src and alignment_tests(c) - set(m.OPERAND_ALIGNMENT_TESTED) == {("gw_dispatch", "X", 16)}
+
+
 def test_cases_are_well_formed():
     ids = [switchback_cases.case_id(c) for c in switchback_cases.CASES]
     assert len(ids) == len(set(ids))
     for c in switchback_cases.CASES:
         assert c["op"] in ("forward", "dequant", "grad_w", "transpose"), c
+        assert isinstance(c["variant"], str) and set(c) <= {"op", "kernel", "variant", "M", "N", "K", "lead", "dt", "bias", "generic", "view", "off", "special"}, c
+        for operand, off in c.get("off", {}).items():
+            assert 0 < off < 16 and operand in {"forward": "x w bias out ws", "dequant": "w out", "grad_w": "dy x dW ws", "transpose": "x out"}[c["op"]].split(), c
         assert c["dt"] in ("f16", "bf16", "f32"), c
         assert ("M" in c) != ("lead" in c) or c["op"] == "dequant", c
 
