@@ -17,6 +17,18 @@
 //                             per slot stalls the MFMA stream, measured 171 vs 94 us)
 //       slot  B2 = 100        vmcnt(16) + barrier: tile j+1 (issued one k-step ago) visible
 //       slots 100 .. 115      the 16 fragment reads of slice 0 of tile j+1
+// The end of K: a k-step with j + 2 >= nk has no tile left to fetch and issues NO piece (the k position is never clamped: nothing is
+// read past the end of K, and the last two k-steps leave the L2 -> LDS path alone); barrier 2 of k-step nk-2 waits with vmcnt(0), k-step
+// nk-1 has no barrier at all.  Those two k-steps hold nothing wave-specific and exist once, behind the per-wave copies of the loop.
+// The tail (depth 1): for 16-bit outputs of the weight type, unsplit, on the 256-wide tiles (FM = 8 and FM = 4), the LAST k-step runs its
+// MFMAs m-group by m-group (per accumulator still slice 0, then slice 1: same bits) and part g of the epilogue -- accumulator reads, bias,
+// the one rounding, pack, staging, 16-byte "sc1" stores -- goes out in the filler slots behind group g's last MFMA, staged in the LDS
+// stage of tile nk-2, which is dead by then; behind the loop only the last group's part is left.  The stores of seven eighths of the
+// tile so start under the last k-step's MFMAs instead of behind them.  Kept on the epilogue behind the loop (compile time: split-K
+// partials, the int8 and outlier forms, the 224 / 192 / 160-wide columns of k_gemm_dense_nb, whose 2 FN slots per group do not hold a
+// part's FN + 8 fillers; run time: f32 and other-type outputs, N % 8 != 0 or an unaligned output, N >= 2^23, one k-step per slice).
+// A tail of depth 2 (both last k-steps, weight fragments of two tiles in the fragment file) is not built: see DESIGN.md 5.3b.
+// Every MFMA of the k-steps is issued from assembly with its accumulator pinned to an AGPR tuple, as in gemm_dense128.h.
 // Measured (tools/exp/ab_dense.py, profiles/r02_dense_ab.txt): 4096^3 bf16 94-96 us against 86-90 us for the vendor BLAS on
 // the same operands (k-loop 81.7 us per 64 k-steps vs 83; the 32 MB store burst of the epilogue costs 8 us here) and
 // 116-124 us for the fused k_gemm256s.
@@ -45,7 +57,7 @@ template <int N, class F> __device__ __forceinline__ void gd_static_for(F &&f) {
     gd_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F &&>(f));
 }
 
-constexpr int GD_LDS = 4 * P_IMG;   // A0 A1 B0 B1; the epilogue's store staging (4 x 16.5 KiB) fits inside
+constexpr int GD_LDS = 4 * P_IMG;   // A0 A1 B0 B1; the epilogue's store staging (4 x 16.5 KiB; under the last k-step 4 x 8.25 KiB of the dead stage) fits inside
 
 // Slot plan of a k-step for a wave tile of 8 (n) x FM (m) fragments of 16 x 16: NS = 16 FM slots, NR = 8 + FM fragment reads
 // per k32 slice, NP = 8 + FM LDS-DMA pieces per wave (A: FM, B: 8).
@@ -209,66 +221,84 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
     };
     f32x4 acc[FN][FM];   // never zero-filled: the first k-step's slice-0 MFMAs take a literal-zero C operand
 
-    auto kbytes = [&](int t) { return (t < nk ? t : nk - 1) << 7; };   // past the end: the last tile again (never used)
+    auto kbytes = [&](int t) { return t << 7; };   // only ever asked for a tile of the slice: no k-step issues a piece past its end
 
-    // ---- prologue: tile 0 -> stage 0, tile 1 -> stage 1; slice 0 of tile 0 -> registers
+    // ---- prologue: tile 0 -> stage 0, tile 1 (if the slice has one) -> stage 1; slice 0 of tile 0 -> registers
     {
         const DmaCtx c0 = dma_ctx();
         gd_static_for<Plan::NP>([&](auto q) { issue_piece(q, 0, 0, c0); });
-        gd_static_for<Plan::NP>([&](auto q) { issue_piece(q, 1, kbytes(1), c0); });
+        if (nk > 1) {
+            gd_static_for<Plan::NP>([&](auto q) { issue_piece(q, 1, kbytes(1), c0); });
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Plan::NP) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Plan::NP) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     gd_static_for<Plan::NR>([&](auto n) { read_one(0, std::integral_constant<int, 0>{}, n); });
 
+    // MFMAs from assembly, the accumulator pinned to its AGPR tuple (as in gemm_dense128.h and gemm_i8_inplace.h): with the epilogue's
+    // accumulator reads beside the last k-step's MFMAs the allocator otherwise lets accumulators and fragments wander between the files
+    auto mfma_acc = [&](f32x4 &c, const Frag &a, const Frag &b) {
+        if constexpr (I8) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+        else if constexpr (std::is_same_v<T, bf16_t>) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+        else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+    };
+    auto mfma_zero = [&](f32x4 &c, const Frag &a, const Frag &b) {
+        if constexpr (I8) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+        else if constexpr (std::is_same_v<T, bf16_t>) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+        else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+    };
+
     // ---- one k-step = Plan::NS fenced slots.  Stage C holds tile j, stage Nn tile j+1 (landing); WO = the wave's slot offset.
-    auto kstep = [&](auto cc, auto first, auto wo_, int j, const DmaCtx &dc) {
-        constexpr int C = decltype(cc)::value, Nn = C ^ 1, WO = decltype(wo_)::value;
+    // MODE 0: a k-step with j + 2 < nk -- the slot plan above.  MODE 1: k-step nk-2 -- no tile is left to fetch, so it issues no piece, and
+    // barrier 2 waits for everything in flight (vmcnt(0): the pieces of tile nk-1, issued one k-step ago).  MODE 2: k-step nk-1 under today's
+    // epilogue -- no piece, no barrier, no reads of a next tile.  MODE 1 and 2 issue nothing wave-specific: they exist once, behind the
+    // per-wave copies of the loop, and take their stage as a run-time value.
+    auto kstep = [&](auto cc, auto first, auto mode_, auto wo_, int j, const DmaCtx &dc) {
+        constexpr int WO = decltype(wo_)::value, MODE = decltype(mode_)::value;
         constexpr bool FIRST = decltype(first)::value;
-        const int kb2 = __builtin_amdgcn_readfirstlane(kbytes(j + 2));
+        const int C = cc, Nn = C ^ 1;
+        int kb2 = 0;
+        if constexpr (MODE == 0) kb2 = __builtin_amdgcn_readfirstlane(kbytes(j + 2));
         gd_static_for<Plan::NS>([&](auto tt) {
             constexpr int t = decltype(tt)::value, ks = t / (FN * FM), f = (t % (FN * FM)) / FM, g = t % FM;
-            if constexpr (t == Plan::B1) {
+            if constexpr (t == Plan::B1 && MODE != 2) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
-            if constexpr (t == Plan::B2) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Plan::NP) : "memory");
+            if constexpr (t == Plan::B2 && MODE != 2) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MODE == 0 ? Plan::NP : 0) : "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
-            if constexpr (I8) {
-                typedef int i32x4_t __attribute__((ext_vector_type(4)));
-                i32x4_t c = {0, 0, 0, 0};
-                if constexpr (!(FIRST && ks == 0)) c = __builtin_bit_cast(i32x4_t, acc[f][g]);
-                acc[f][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, wf[ks][f]),
-                                                                                        __builtin_bit_cast(i32x4_t, xf[ks][g]), c, 0, 0, 0));
-            } else if constexpr (FIRST && ks == 0) {
-                const f32x4 zero = {0, 0, 0, 0};
-                acc[f][g] = Mfma16<T>::run(wf[ks][f], xf[ks][g], zero);
-            } else {
-                acc[f][g] = Mfma16<T>::run(wf[ks][f], xf[ks][g], acc[f][g]);
-            }
+            if constexpr (FIRST && ks == 0) mfma_zero(acc[f][g], wf[ks][f], xf[ks][g]);
+            else mfma_acc(acc[f][g], wf[ks][f], xf[ks][g]);
             if constexpr ((t % Plan::RS1) == 0 && t / Plan::RS1 < Plan::NR)
                 read_one(C, std::integral_constant<int, 1>{}, std::integral_constant<int, (t / Plan::RS1) % Plan::NR>{});
-            if constexpr (t >= Plan::R0 && t < Plan::R0 + Plan::NR)
+            if constexpr (MODE != 2 && t >= Plan::R0 && t < Plan::R0 + Plan::NR)
                 read_one(Nn, std::integral_constant<int, 0>{}, std::integral_constant<int, (t - Plan::R0) % Plan::NR>{});
-            if constexpr (t >= Plan::D0 && t < Plan::D0 + Plan::NP * Plan::DS && ((t - Plan::D0) % Plan::DS) == WO)
+            if constexpr (MODE == 0 && t >= Plan::D0 && t < Plan::D0 + Plan::NP * Plan::DS && ((t - Plan::D0) % Plan::DS) == WO)
                 issue_piece(std::integral_constant<int, ((t - Plan::D0) / Plan::DS) % Plan::NP>{}, C, kb2, dc);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
+    using Mode0 = std::integral_constant<int, 0>;
+    using Mode1 = std::integral_constant<int, 1>;
+    using Mode2 = std::integral_constant<int, 2>;
+    // the k-steps that fetch: 0 .. nk-3, one copy of the loop per wave
     auto main_loop = [&](auto wo) {
+        if (nk < 3) return;
         const DmaCtx dc = dma_ctx();
-        kstep(std::integral_constant<int, 0>{}, std::true_type{}, wo, 0, dc);
+        kstep(std::integral_constant<int, 0>{}, std::true_type{}, Mode0{}, wo, 0, dc);
         int j = 1;
-        for (; j + 1 < nk; j += 2) {
-            kstep(std::integral_constant<int, 1>{}, std::false_type{}, wo, j, dc);
-            kstep(std::integral_constant<int, 0>{}, std::false_type{}, wo, j + 1, dc);
+        for (; j + 3 < nk; j += 2) {
+            kstep(std::integral_constant<int, 1>{}, std::false_type{}, Mode0{}, wo, j, dc);
+            kstep(std::integral_constant<int, 0>{}, std::false_type{}, Mode0{}, wo, j + 1, dc);
         }
-        if (j < nk) kstep(std::integral_constant<int, 1>{}, std::false_type{}, wo, j, dc);
+        if (j + 2 < nk) kstep(std::integral_constant<int, 1>{}, std::false_type{}, Mode0{}, wo, j, dc);
     };
     if constexpr (Plan::DS == 4) {
         if (wave == 0) main_loop(std::integral_constant<int, 0>{});
@@ -279,7 +309,130 @@ __device__ __forceinline__ void gemm_dense_body(const T *__restrict__ X, const T
         if ((wave & 1) == 0) main_loop(std::integral_constant<int, 0>{});
         else main_loop(std::integral_constant<int, 1>{});
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+    // ---- the tail (depth 1): the last k-step with the 16-bit epilogue under it.  Forms: 16-bit weights, unsplit, 256-wide tiles (FM = 8 and 4);
+    // at run time 16-bit outputs of the weight type through the 16-byte store path, and a slice of two k-steps or more.  Everything else --
+    // split-K partials, f32 and other-type outputs, the scalar store path, the int8 and outlier forms, the 224 / 192 / 160-wide columns
+    // (2 FN slots per m-group do not hold a part's FN + 8 fillers) -- keeps the epilogue below.
+    constexpr bool TAIL = !SPLITK && !I8 && OUTL == 0 && FN == 8;
+    bool tail_ok = false;
+    if constexpr (TAIL)
+        tail_ok = nk >= 2 && out_dtype == (std::is_same_v<T, f16_t> ? MBNB_F16 : MBNB_BF16) && (N % 8 == 0) &&
+                  ((reinterpret_cast<uintptr_t>(out_v) & 15) == 0) && N < ((int64_t)1 << 23);
+    // the bias of the tail, requested a whole k-step before its first use
+    u32x2 bias_t[TAIL ? FN : 1];
+    if constexpr (TAIL) {
+        if (tail_ok && bias != nullptr) {
+            const uint16_t *bp = reinterpret_cast<const uint16_t *>(bias);
+#pragma unroll
+            for (int f = 0; f < FN; f++) {
+                const int64_t n = n0 + wn * 16 * FN + 16 * f + 4 * fq;
+                if (n + 4 <= N && (reinterpret_cast<uintptr_t>(bp + n) & 7) == 0) bias_t[f] = *reinterpret_cast<const u32x2 *>(bp + n);
+                else {
+                    uint32_t t[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) t[e] = bp[n + e < N ? n + e : N - 1];
+                    bias_t[f] = u32x2{t[0] | (t[1] << 16), t[2] | (t[3] << 16)};
+                }
+            }
+        }
+    }
+    {
+        const DmaCtx none{};
+        if (nk == 2) kstep(std::integral_constant<int, 0>{}, std::true_type{}, Mode1{}, std::integral_constant<int, 0>{}, 0, none);
+        else if (nk > 2) kstep(nk & 1, std::false_type{}, Mode1{}, std::integral_constant<int, 0>{}, nk - 2, none);
+        if (nk == 1) kstep(std::integral_constant<int, 0>{}, std::true_type{}, Mode2{}, std::integral_constant<int, 0>{}, 0, none);
+        else if (!tail_ok) kstep((nk - 1) & 1, std::false_type{}, Mode2{}, std::integral_constant<int, 0>{}, nk - 1, none);
+    }
+    if constexpr (TAIL) {
+        // The last k-step, m-group by m-group: slot t is the MFMA of (g, ks, f) = (t / 2 FN, (t / FN) % 2, t % FN) -- per accumulator slice 0 then
+        // slice 1, as everywhere -- so group g is complete after slot 2 FN (g + 1) - 1, and group 0 after 2 FN slots: its slice-1 operands are
+        // the first FN + 1 of the fragment reads (x0, w0 .. w7, then x1 .. x7, one per slot from slot 0; w_f is asked for FN - 1 slots ahead).
+        // Behind group g's last MFMA part g of the epilogue goes out, one filler per slot of the next group's 2 FN: FN x (four accumulator
+        // reads, bias, the one rounding, pack, 8-byte staging write), 4 x (read back 4 rows x 256 B), 4 x (one 16-byte "sc1" store).
+        // Staging: stage C ^ 1 held tile nk-2, whose fragments every wave had in registers at barrier 1 of k-step nk-2, and nothing has been
+        // fetched into it since (no dead pieces); each wave has 2 x 16 rows x 264 B of it to itself (waves 0 / 1 in the A image, 2 / 3 in the B
+        // image), the two halves taking turns.  No barrier and no wait is left in this k-step.  The stores are buffer stores: the row goes
+        // into the per-lane offset, the descriptor ends at the tile's last row inside M, so rows past M fall to its range check (as the
+        // operands' rows do on the way in) and a lane whose columns lie past N carries an offset that is out of range for every row.
+        auto tail_step = [&](auto wb_t, const int C) {
+            constexpr bool WB = decltype(wb_t)::value;
+            constexpr int ROWB = 264, GS = 2 * FN;
+            int tid2 = threadIdx.x;
+            asm volatile("" : "+v"(tid2));      // none of this address arithmetic is hoisted above the loop
+            const int lane_e = tid2 & 63, er16 = lane_e & 15, efq = lane_e >> 4;
+            char *stg = smem + (wn ? P_B : P_A) + (C ^ 1) * P_IMG + wm * (2 * 16 * ROWB);
+            char *st_w = stg + er16 * ROWB + 8 * efq;
+            const char *st_r = stg + efq * ROWB + er16 * 16;
+            const int64_t m_w = m0 + wm * 16 * FM;
+            int64_t rows = M - m_w;
+            rows = rows < 0 ? 0 : (rows > 16 * FM ? 16 * FM : rows);
+            const uint64_t po = reinterpret_cast<uint64_t>(static_cast<uint16_t *>(out_v) + m_w * N);
+            i32x4_t rs_o;
+            rs_o[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)po);
+            rs_o[1] = __builtin_amdgcn_readfirstlane((int)(uint32_t)(po >> 32));
+            rs_o[2] = __builtin_amdgcn_readfirstlane((int)(rows * N * 2));
+            rs_o[3] = 0x00020000;
+            const int rowstep = __builtin_amdgcn_readfirstlane((int)(N * 2));
+            const int64_t n = n0 + wn * 16 * FN + er16 * 8;
+            const int voff0 = n < N ? (int)((efq * N + n) * 2) : (int)0x80000000;
+            u32x4 piece[4];
+            auto filler = [&](auto gg, auto ss) {
+                constexpr int g = decltype(gg)::value, s = decltype(ss)::value, buf = (g & 1) * 16 * ROWB;
+                if constexpr (s < FN) {
+                    float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if constexpr (WB) {
+#pragma unroll
+                        for (int e = 0; e < 4; e++) bv[e] = unpack_lo<T>(bias_t[s][e >> 1] >> (16 * (e & 1)));
+                    }
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        float sv;
+                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(sv) : "a"(acc[s][g][e]));
+                        v[e] = sv + bv[e];
+                    }
+                    const u32x2 pk = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};   // the output type is the weight type: the pack is the rounding
+                    *reinterpret_cast<u32x2 *>(st_w + buf + 32 * s) = pk;
+                } else if constexpr (s < FN + 4) {
+                    constexpr int p = s - FN;
+                    const char *srcp = st_r + buf + p * 4 * ROWB;
+                    const u32x2 lo = *reinterpret_cast<const u32x2 *>(srcp), hi = *reinterpret_cast<const u32x2 *>(srcp + 8);
+                    piece[p] = u32x4{lo[0], lo[1], hi[0], hi[1]};
+                } else if constexpr (s < FN + 8) {
+                    constexpr int p = s - FN - 4;
+                    const int vo = voff0 + (16 * g + 4 * p) * rowstep;
+                    const i32x4_t rs = rs_o;
+                    const u32x4 pv = piece[p];
+                    // (a store of more than 8 bytes needs two wait states before a VALU instruction may write its data registers: the
+                    // compiler cannot count them behind an asm statement, so the statement ends with them)
+                    asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1\n\ts_nop 1" ::"v"(pv), "v"(vo), "s"(rs) : "memory");
+                }
+            };
+            gd_static_for<Plan::NS>([&](auto tt) {
+                constexpr int t = decltype(tt)::value, g = t / GS, ks = (t % GS) / FN, f = t % FN;
+                // With the parts' accumulator reads in between, the allocator moves a group's accumulators into the tuples the previous group
+                // left (v_accvgpr_mov in front of the MFMA).  A VALU write needs two wait states before an MFMA reads the register, and the
+                // compiler cannot count them into an asm statement: the statement brings them along.
+                if constexpr (std::is_same_v<T, bf16_t>) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[f][g]) : "v"(wf[ks][f]), "v"(xf[ks][g]));
+                else asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[f][g]) : "v"(wf[ks][f]), "v"(xf[ks][g]));
+                if constexpr (t < Plan::NR)     // x0, w0 .. w(FN-1), x1 .. x(FM-1) in read_one's numbering (w0, x0 .. x(FM-1), w1 ..)
+                    read_one(C, std::integral_constant<int, 1>{},
+                             std::integral_constant<int, (t == 0 ? 1 : t == 1 ? 0 : t <= FN ? t - 1 + FM : t - FN + 1)>{});
+                if constexpr (t >= GS) filler(std::integral_constant<int, t / GS - 1>{}, std::integral_constant<int, t % GS>{});
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            gd_static_for<GS>([&](auto ss) {    // only the last group's part is left
+                filler(std::integral_constant<int, FM - 1>{}, ss);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        };
+        if (tail_ok) {
+            if (bias != nullptr) tail_step(std::true_type{}, (nk - 1) & 1);
+            else tail_step(std::false_type{}, (nk - 1) & 1);
+            return;
+        }
+    }
 
     // ---- epilogue: acc[f][g][r] = out[m0 + 16 FM wm + 16 g + (lane & 15)][n0 + 16 FN wn + 16 f + 4 (lane >> 4) + r]
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
