@@ -15,12 +15,12 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _native, _sparse_native, _train_native
+from . import _group_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -632,6 +632,93 @@ def matmul_fp4(input: Tensor, weight_packed: Tensor, weight_state: QuantState,
                bias: Optional[Tensor] = None) -> Tensor:
     """Matrix multiplication with FP4-quantized weights (reference functional.py:782-785)."""
     return matmul_4bit(input, weight_packed, weight_state, bias)
+
+
+def _group_rows(A: Tensor, weights, biases, compute_dtype: Optional[torch.dtype]):
+    """What the fused launch of matmul_4bit_grouped needs -- (K, quant_type, blocksize, w_dtype, [(packed, desc, bias, N), ...], keep) --
+    or None where the call is not one row times weights of one format (or where a member would not pass matmul_4bit's own checks:
+    the member-by-member path then raises what matmul_4bit raises).  Whether the kernel takes the shapes is the library's decision."""
+    if torch.is_grad_enabled() and (A.requires_grad or any(b is not None and b.requires_grad for b in biases)):
+        return None
+    if A.device.type != 'cuda' or A.dim() == 0 or A.shape[-1] == 0 or A.numel() != A.shape[-1]:
+        return None
+    K = int(A.shape[-1])
+    first = weights[0][1]
+    qt, blocksize, w_dtype = first.quant_type, first.blocksize, first.dtype
+    if (w_dtype not in _native.DTYPE_CODE or qt not in _native.QUANT_CODE or not isinstance(blocksize, int) or blocksize <= 0
+            or (A.dtype if compute_dtype is None else compute_dtype) != w_dtype):
+        return None
+    K_weight = _padded(K, blocksize)
+    rows, keep = [], []
+    for (B, state), bias in zip(weights, biases):
+        if (state.quant_type != qt or state.blocksize != blocksize or state.dtype != w_dtype or len(state.shape) != 2
+                or int(state.shape[1]) != K or B.device != A.device or B.dtype != torch.uint8 or not B.is_contiguous()):
+            return None
+        N = int(state.shape[0])
+        am = state.absmax
+        if N <= 0 or B.numel() * 2 < N * K_weight or am.numel() != N * (K_weight // blocksize):
+            return None
+        try:
+            desc = _absmax_desc(am if am.device == A.device else am.to(A.device), state.state2, keep)
+        except ValueError:
+            return None
+        if bias is not None:
+            bias = _as(bias, w_dtype, A.device)   # functional.py:765-766, as matmul_4bit
+            keep.append(bias)
+        rows.append((B, desc, bias, N))
+    return K, qt, blocksize, w_dtype, rows, keep
+
+
+def matmul_4bit_grouped(
+    A: Tensor,
+    weights: Sequence[Tuple[Tensor, QuantState]],
+    biases: Optional[Sequence[Optional[Tensor]]] = None,
+    compute_dtype: Optional[torch.dtype] = None,
+) -> Tuple[Tensor, ...]:
+    """
+    ``tuple(matmul_4bit(A, packed, state, bias, compute_dtype) for (packed, state), bias in zip(weights, biases))`` -- the same
+    values bit for bit, the same errors -- with ONE kernel launch per 16 members where A is a single row (the decode step of a
+    transformer block: q / k / v share their input, and so do gate / up).
+
+    `weights` is a sequence of ``(packed, QuantState)`` pairs, `biases` one Tensor or None per member (default: no bias).
+    An empty sequence returns ``()``.
+
+    The fused launch (libmbnb_group.so, k_gemv4_group: the row body of matmul_4bit's own M = 1 kernel behind a member table)
+    serves a call in which A folds to one row, no gradient is wanted, every member has the same quant_type, blocksize and
+    weight dtype, and the output dtype equals the weight dtype; the library then decides on the shapes (blocksize 64, K a
+    multiple of 64 in 1024 ... 16384, 16-bit dtype, aligned operands, all absmax plain or all double-quantised) and a chunk it
+    declines runs member by member.  Everything else -- more rows, a gradient (differentiable through matmul_4bit's autograd
+    function), mixed formats, f32 weights, another compute_dtype -- is the member-by-member loop above.
+
+    On the fused path the outputs are VIEWS of one allocation of sum(N) elements: writing to one in place never touches another,
+    but each keeps the whole allocation alive.
+    """
+    weights = list(weights)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    if len(biases) != len(weights):
+        raise ValueError(f"matmul_4bit_grouped: {len(weights)} weights but {len(biases)} biases")
+    if not weights:
+        return ()
+    plan = _group_rows(A, weights, biases, compute_dtype)
+    if plan is None:
+        return tuple(matmul_4bit(A, B, state, bias, compute_dtype) for (B, state), bias in zip(weights, biases))
+    K, qt, blocksize, w_dtype, rows, keep = plan
+    x = _as(A.reshape(1, K), w_dtype)             # prepared once for all members (matmul_4bit: A.to(weight dtype), contiguous)
+    out = torch.empty(sum(r[3] for r in rows), dtype=w_dtype, device=A.device)
+    table, outs, first = [], [], out.data_ptr()
+    esize, o = out.element_size(), 0
+    for B, desc, bias, N in rows:
+        table.append((B.data_ptr(), desc.absmax_f32 or 0, desc.absmax_i8 or 0, desc.absmax2 or 0,
+                      0 if bias is None else bias.data_ptr(), first + o * esize, N, desc.blocksize2, 0))
+        outs.append(out[o:o + N].view(*A.shape[:-1], N))
+        o += N
+    with on_device(A.device):
+        launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+    for c, ok in enumerate(launched):
+        if not ok:    # the library declined this chunk before launching anything: its members one by one
+            for i in range(c * _group_native.MAX_MEMBERS, min((c + 1) * _group_native.MAX_MEMBERS, len(rows))):
+                outs[i] = matmul_4bit(A, weights[i][0], weights[i][1], biases[i], compute_dtype)
+    return tuple(outs)
 
 
 def matmul_int8(A: Tensor, B: Tensor, A_scales: Tensor, B_scales: Tensor,
