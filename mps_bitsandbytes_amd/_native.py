@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libmbnb_hip.so")
 
 ABI_VERSION = 2   # include/mbnb_hip.h MBNB_ABI_VERSION
 _PREFIX, _CHECK_PREFIX = "mbnb", "mps_bitsandbytes_amd"
-F16, BF16, F32 = 0, 1, 2        # the element-type codes of all six headers
+F16, BF16, F32 = 0, 1, 2        # the element-type codes of all seven headers
 NF4, FP4 = 0, 1
 W_INT8_ROWWISE, W_FP8_E4M3, W_DENSE = 2, 3, 4   # the other weight formats of mbnb_linear_grad_input
 GRAD_TRANSPOSE_ONLY = 2                         # its flags word: the transposed dequantise pass alone

@@ -1,4 +1,4 @@
-// host.h — what the host side of all six libraries shares: the thread-local error text behind each library's *_last_error(), the
+// host.h — what the host side of all seven libraries shares: the thread-local error text behind each library's *_last_error(), the
 // launch check, and the small argument predicates.  Host code only; the two element types come from elem_types.h.
 //
 // Included by the ONE source file of a library that owns its error text: the source of each satellite library, and api.hip for

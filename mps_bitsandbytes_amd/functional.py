@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _group_native, _native, _sparse_native, _train_native
+from . import _group_native, _lora_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -703,7 +703,20 @@ def matmul_4bit_grouped(
     if plan is None:
         return tuple(matmul_4bit(A, B, state, bias, compute_dtype) for (B, state), bias in zip(weights, biases))
     K, qt, blocksize, w_dtype, rows, keep = plan
-    x = _as(A.reshape(1, K), w_dtype)             # prepared once for all members (matmul_4bit: A.to(weight dtype), contiguous)
+    x, table, outs = _group_table(A, K, w_dtype, rows)
+    with on_device(A.device):
+        launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+    for c, ok in enumerate(launched):
+        if not ok:    # the library declined this chunk before launching anything: its members one by one
+            for i in range(c * _group_native.MAX_MEMBERS, min((c + 1) * _group_native.MAX_MEMBERS, len(rows))):
+                outs[i] = matmul_4bit(A, weights[i][0], weights[i][1], biases[i], compute_dtype)
+    return tuple(outs)
+
+
+def _group_table(A: Tensor, K: int, w_dtype: torch.dtype, rows):
+    """(x, table, outs) of a fused grouped launch over _group_rows' `rows`: A prepared once for all members (matmul_4bit: A.to(weight
+    dtype), contiguous), the Member field tuples, and the outputs -- views of ONE allocation of sum(N) elements."""
+    x = _as(A.reshape(1, K), w_dtype)
     out = torch.empty(sum(r[3] for r in rows), dtype=w_dtype, device=A.device)
     table, outs, first = [], [], out.data_ptr()
     esize, o = out.element_size(), 0
@@ -712,12 +725,106 @@ def matmul_4bit_grouped(
                       0 if bias is None else bias.data_ptr(), first + o * esize, N, desc.blocksize2, 0))
         outs.append(out[o:o + N].view(*A.shape[:-1], N))
         o += N
+    return x, table, outs
+
+
+def _lora_ranks(A: Tensor, K: int, w_dtype: torch.dtype, rows, adapters):
+    """One (lora_A, lora_B, R, scaling) or None per member where the fused adapter launch can take the adapters as they are -- every
+    tensor on A's device, in the weight dtype, contiguous, shaped [R, K] and [N, R], no gradient wanted -- else None.  Whether the
+    kernels take the ranks and the alignment is the library's decision."""
+    ranks = []
+    for (_, _, _, N), adapter in zip(rows, adapters):
+        if adapter is None:
+            ranks.append(None)
+            continue
+        lora_A, lora_B, scaling = adapter
+        R = int(lora_A.shape[0]) if lora_A.dim() == 2 else -1
+        for t, shape in ((lora_A, (R, K)), (lora_B, (N, R))):
+            if (t.device != A.device or t.dtype != w_dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                    or (t.requires_grad and torch.is_grad_enabled())):
+                return None
+        ranks.append((lora_A, lora_B, R, float(scaling)) if R > 0 else None)
+    return ranks
+
+
+def _lora_composed(A: Tensor, B: Tensor, state: QuantState, bias: Optional[Tensor], adapter, compute_dtype: Optional[torch.dtype]) -> Tensor:
+    """One member of matmul_4bit_lora_grouped in its composed form: matmul_4bit (HIP kernels, differentiable in A and the bias) plus the
+    adapter in torch ops (torch's GEMM; autograd gives lora_A, lora_B and A their gradients)."""
+    y = matmul_4bit(A, B, state, bias, compute_dtype)
+    if adapter is None:
+        return y
+    lora_A, lora_B, scaling = adapter
+    x = A if A.dtype == state.dtype else A.to(state.dtype)        # the row as matmul_4bit feeds it
+    if x.dtype != lora_A.dtype:
+        x = x.to(lora_A.dtype)
+    u = ((x @ lora_A.t()) @ lora_B.t()) * scaling
+    return y + (u if u.dtype == y.dtype else u.to(y.dtype))
+
+
+def matmul_4bit_lora_grouped(
+    A: Tensor,
+    weights: Sequence[Tuple[Tensor, QuantState]],
+    adapters: Sequence[Optional[Tuple[Tensor, Tensor, float]]],
+    biases: Optional[Sequence[Optional[Tensor]]] = None,
+    compute_dtype: Optional[torch.dtype] = None,
+) -> Tuple[Tensor, ...]:
+    """
+    `matmul_4bit_grouped` for layers that carry un-merged LoRA adapters (a LoRA trained over a 4-bit base cannot be merged into it):
+    per member, ``A @ dequant(W)^T + bias + float32(scaling) * (A @ lora_A^T) @ lora_B^T``.
+
+    `adapters` holds one entry per member: ``None`` or ``(lora_A [r, K], lora_B [N, r], scaling)``.  Returns a tuple of outputs, as
+    `matmul_4bit_grouped` does.  With every adapter ``None`` the call IS `matmul_4bit_grouped`.
+
+    What is promised is a BOUND, not bit-equality between the paths (unlike `matmul_4bit_grouped`): each element lies within the
+    elementwise bounds of DESIGN.md 17 around the float64 value of the expression above, on whichever path computed it.  A member
+    whose adapter is ``None`` equals `matmul_4bit` bit for bit on every path.
+
+    The fused path (libmbnb_lora.so) makes TWO launches per 16 members: `k_lora_down` (t = lora_A . x in f32 for every adapter row of
+    every member) and `k_gemv4_group_lora` (the grouped GEMV's rows, each adding ``scaling * lora_B[n, :] . t`` to its f32 accumulator
+    before the bias and the one rounding).  It serves a call that `matmul_4bit_grouped` would fuse (A folds to one row, no gradient
+    wanted, one quant_type / blocksize / weight dtype, output dtype = weight dtype) in which every adapter tensor is on A's device,
+    in the weight dtype, contiguous, shaped ``[r, K]`` / ``[N, r]`` and wants no gradient; the library then decides on the shapes
+    (those of the grouped GEMV, and 1 <= r <= 256 with aligned operands), and a chunk it declines runs through the composed form.
+    The outputs are views of one allocation, the f32 workspaces slices of another.
+
+    Everything else -- more rows, a wanted gradient, mixed formats, r > 256, another dtype -- runs ONE composed form per member:
+    `matmul_4bit` (this library's HIP kernels, differentiable in A and the bias) plus
+    ``((A.to(T) @ lora_A.t()) @ lora_B.t()) * scaling`` in torch ops.  That half is torch's GEMM, NOT a HIP kernel of this library;
+    autograd gives lora_A, lora_B and A their gradients through it.  An efficient adapter path for prefill and training is not
+    part of this function.
+    """
+    weights, adapters = list(weights), list(adapters)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    if len(biases) != len(weights):
+        raise ValueError(f"matmul_4bit_lora_grouped: {len(weights)} weights but {len(biases)} biases")
+    if len(adapters) != len(weights):
+        raise ValueError(f"matmul_4bit_lora_grouped: {len(weights)} weights but {len(adapters)} adapters")
+    if all(adapter is None for adapter in adapters):
+        return matmul_4bit_grouped(A, weights, biases, compute_dtype)
+
+    def composed(i):
+        return _lora_composed(A, weights[i][0], weights[i][1], biases[i], adapters[i], compute_dtype)
+
+    plan = _group_rows(A, weights, biases, compute_dtype)
+    ranks = None if plan is None else _lora_ranks(A, plan[0], plan[3], plan[4], adapters)
+    if ranks is None:
+        return tuple(composed(i) for i in range(len(weights)))
+    K, qt, blocksize, w_dtype, rows, keep = plan
+    x, table, outs = _group_table(A, K, w_dtype, rows)
+    t = torch.empty(sum(r[2] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
+    rank_table, t0, o = [], t.data_ptr(), 0
+    for r in ranks:
+        if r is None:
+            rank_table.append(_lora_native.NO_ADAPTER)
+        else:
+            rank_table.append((r[0].data_ptr(), r[1].data_ptr(), t0 + 4 * o, r[2], r[3]))
+            o += r[2]
     with on_device(A.device):
-        launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+        launched = _lora_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
     for c, ok in enumerate(launched):
-        if not ok:    # the library declined this chunk before launching anything: its members one by one
-            for i in range(c * _group_native.MAX_MEMBERS, min((c + 1) * _group_native.MAX_MEMBERS, len(rows))):
-                outs[i] = matmul_4bit(A, weights[i][0], weights[i][1], biases[i], compute_dtype)
+        if not ok:    # the library declined this chunk before launching anything: its members in the composed form
+            for i in range(c * _lora_native.MAX_MEMBERS, min((c + 1) * _lora_native.MAX_MEMBERS, len(rows))):
+                outs[i] = composed(i)
     return tuple(outs)
 
 
