@@ -128,24 +128,30 @@ __global__ __launch_bounds__(256) void k_grad_generic(const T *__restrict__ dY, 
         __syncthreads();
     }
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t m0 = (int64_t)blockIdx.y * GRAD_GM;
-    if (k >= K) return;
-    const T *y[GRAD_GM];
+    if (k >= K) return;   // no barrier below: the code table's is above
+    // grid.y holds at most 65535 row groups: a workgroup walks on by the grid's height, as the forward's generic kernels do
+    for (int64_t m0 = (int64_t)blockIdx.y * GRAD_GM; m0 < M; m0 += (int64_t)gridDim.y * GRAD_GM) {
+        const T *y[GRAD_GM];
 #pragma unroll
-    for (int i = 0; i < GRAD_GM; i++) y[i] = dY + (m0 + i < M ? m0 + i : M - 1) * N;
-    float acc[GRAD_GM] = {};
-    for (int64_t n = 0; n < N; n++) {
-        const float w = grad_decode<T, FMT, NESTED>(W, am, scales, lut, n, k, ldq, bs_shift);
+        for (int i = 0; i < GRAD_GM; i++) y[i] = dY + (m0 + i < M ? m0 + i : M - 1) * N;
+        float acc[GRAD_GM] = {};
+        for (int64_t n = 0; n < N; n++) {
+            const float w = grad_decode<T, FMT, NESTED>(W, am, scales, lut, n, k, ldq, bs_shift);
 #pragma unroll
-        for (int i = 0; i < GRAD_GM; i++) acc[i] = fmaf(to_f32(y[i][n]), w, acc[i]);
+            for (int i = 0; i < GRAD_GM; i++) acc[i] = fmaf(to_f32(y[i][n]), w, acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < GRAD_GM; i++)
+            if (m0 + i < M) dX[(m0 + i) * K + k] = (O)to_f32(from_f32<T>(acc[i]));   // one rounding to the weight dtype, then the cast
     }
-#pragma unroll
-    for (int i = 0; i < GRAD_GM; i++)
-        if (m0 + i < M) dX[(m0 + i) * K + k] = (O)to_f32(from_f32<T>(acc[i]));   // one rounding to the weight dtype, then the cast
 }
 
 // ------------------------------------------------------------------------------------- host side
 static bool is4(int fmt) { return fmt == MBNB_NF4 || fmt == MBNB_FP4; }
+
+// the words of the variant record (mbnb_last_kernel's second string): which instantiation a launch took
+template <typename T> constexpr bool kIsBf16 = false;
+template <> constexpr bool kIsBf16<bf16_t> = true;
 
 // the pass serves this weight (the caller checks W's alignment)
 static bool grad_t_shape(int64_t N, int64_t K, int fmt, int blocksize) {
@@ -172,8 +178,12 @@ static int launch_dequant_t(const uint8_t *W, const AbsmaxView &am, const float 
     const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((K + 255) / 256));
     const int vec = (N % 8 == 0) && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     const int sh = is4(FMT) ? __builtin_ctz((unsigned)blocksize) : 0;
-    if (is4(FMT) && am.i8) hipLaunchKernelGGL((k_dequant_t<T, FMT, true>), grid, dim3(256), 0, st, W, am, scales, N, K, ldq, sh, out, vec, write_through);
+    const bool nested = is4(FMT) && am.i8;
+    if (nested) hipLaunchKernelGGL((k_dequant_t<T, FMT, true>), grid, dim3(256), 0, st, W, am, scales, N, K, ldq, sh, out, vec, write_through);
     else hipLaunchKernelGGL((k_dequant_t<T, FMT, false>), grid, dim3(256), 0, st, W, am, scales, N, K, ldq, sh, out, vec, write_through);
+    // (on the dense path the GEMM's own variant replaces this one)
+    set_kernel_variant("grad_t %s %s %s %s", FMT == MBNB_NF4 ? "nf4" : FMT == MBNB_FP4 ? "fp4" : FMT == MBNB_W_INT8_ROWWISE ? "int8" : FMT == MBNB_W_FP8_E4M3 ? "fp8" : "dense",
+                       kIsBf16<T> ? "bf16" : "f16", nested ? "nested" : "plain", vec ? "vec" : "scalar");
     return check_launch("linear_grad_input(transpose)");
 }
 
@@ -192,16 +202,20 @@ static int dequant_t_dispatch(int fmt, const uint8_t *W, const AbsmaxView &am, c
 template <typename T, typename O, int FMT>
 static void launch_generic_fmt(const T *dY, int64_t M, int64_t N, const uint8_t *W, const AbsmaxView &am, const float *scales, int64_t K, int64_t ldq,
                                int sh, O *dX, hipStream_t st) {
-    const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((M + GRAD_GM - 1) / GRAD_GM));
-    if (is4(FMT) && am.i8) hipLaunchKernelGGL((k_grad_generic<T, O, FMT, true>), grid, dim3(256), 0, st, dY, M, N, W, am, scales, K, ldq, sh, dX);
+    const int64_t groups = (M + GRAD_GM - 1) / GRAD_GM;
+    const dim3 grid((unsigned)((K + 255) / 256), (unsigned)(groups < 65535 ? groups : 65535));   // the kernel walks the row groups past grid.y
+    const bool nested = is4(FMT) && am.i8;
+    if (nested) hipLaunchKernelGGL((k_grad_generic<T, O, FMT, true>), grid, dim3(256), 0, st, dY, M, N, W, am, scales, K, ldq, sh, dX);
     else hipLaunchKernelGGL((k_grad_generic<T, O, FMT, false>), grid, dim3(256), 0, st, dY, M, N, W, am, scales, K, ldq, sh, dX);
+    set_kernel_variant("grad_generic %s %s>%s %s", FMT == MBNB_NF4 ? "nf4" : FMT == MBNB_FP4 ? "fp4" : FMT == MBNB_W_INT8_ROWWISE ? "int8" : FMT == MBNB_W_FP8_E4M3 ? "fp8" : "dense",
+                       sizeof(T) == 4 ? "f32" : kIsBf16<T> ? "bf16" : "f16", sizeof(O) == 4 ? "f32" : kIsBf16<O> ? "bf16" : "f16", nested ? "nested" : "plain");
 }
 
 template <typename T, typename O>
 static int launch_generic(int fmt, const T *dY, int64_t M, int64_t N, const uint8_t *W, const AbsmaxView &am, const float *scales, int64_t K,
                           int64_t ldq, int blocksize, O *dX, hipStream_t st) {
-    if ((K + 255) / 256 > 0x7FFFFFFF || (M + GRAD_GM - 1) / GRAD_GM > 65535) {
-        set_error("linear_grad_input: the generic kernel takes at most %d rows", 65535 * GRAD_GM);
+    if ((K + 255) / 256 > 0x7FFFFFFF) {
+        set_error("linear_grad_input: the generic kernel takes at most %lld columns", (long long)0x7FFFFFFF * 256);
         return MBNB_ERR_UNSUPPORTED;
     }
     const int sh = is4(fmt) ? __builtin_ctz((unsigned)blocksize) : 0;

@@ -1,11 +1,13 @@
 """
 Guarded allocations for the GPU tests that run a kernel form inside guard bands: the quantise / dequantise forms (tests/quant_cases.py)
-and every case of the train and sparse libraries' tables that launches no GEMM (tests/forms.py).
+every case of the train and sparse libraries' tables that launches no GEMM (tests/forms.py), and the input-gradient path, its dense
+route included (tests/grad_cases.py).
 
 ``guarded_alloc`` replaces the name ``torch`` inside ``mps_bitsandbytes_amd.functional`` with a proxy that forwards every attribute
 to torch except ``empty``: the request is carved out of a larger uint8 buffer with a guard band of GUARD bytes on each side, every
 byte of which -- bands and payload -- is set to the proxy's fill; the caller gets the inner view, starting at the byte offset
-modulo 16 the test asked for (``plan``), and the proxy remembers the allocation.  ``check()`` then requires every guard byte to
+modulo 16 the test asked for (``plan``; an offset of 16 and more puts a workspace off its 256-byte alignment), and the proxy remembers
+the allocation.  ``check()`` then requires every guard byte to
 still hold the fill: a store past either end of an output, which the caching allocator's 512-byte rounding would have swallowed,
 is reported with the op, the form, the buffer and the byte offset from the buffer's end (or start).
 
@@ -52,7 +54,7 @@ class Guarded:
 
 def _carve(name, shape, dtype, device, fill, offset):
     esize = torch.empty(0, dtype=dtype).element_size()
-    assert 0 <= offset < 16 and offset % esize == 0, f"{name}: offset {offset} is not a multiple of the element size {esize}"
+    assert 0 <= offset < GUARD and offset % esize == 0, f"{name}: offset {offset} is not a multiple of the element size {esize}"
     numel = 1
     for s in shape:
         numel *= int(s)
@@ -63,7 +65,7 @@ def _carve(name, shape, dtype, device, fill, offset):
     buf.fill_(fill)
     assert buf.data_ptr() % 16 == 0
     view = buf[start:start + nbytes].view(dtype).view(tuple(shape))
-    assert view.data_ptr() % 16 == offset and view.is_contiguous()
+    assert view.data_ptr() % 16 == offset % 16 and view.is_contiguous()      # (an offset of 16 and more: off a 256-byte alignment)
     return Guarded(name, buf, start, nbytes, fill, view)
 
 

@@ -1,6 +1,7 @@
 """
 Host-side closure of tests/gemm_variant_cases.py over the GEMM-family launchers, without a GPU: every variant the sources can
-report (set_kernel_variant in csrc/*.hip and *.h, the macro-generated ones expanded) has a case and no case names another, the
+report (set_kernel_variant in csrc/*.hip and *.h, the macro-generated ones expanded; the gradient path's through tests/grad_cases.py)
+has a case and no case names another, the
 Python restatement of the launchers' conditions gives every case its variant, and the INSTANTIATED, THRESHOLDS and
 ALIGNMENT_TESTED tables hold.  The counts at the end change when a launcher gains or loses an alignment test or an integer limit.
 """
@@ -9,11 +10,13 @@ import os
 import re
 
 from tests import gemm_variant_cases as gv
-from tests import kernel_cases
+from tests import grad_cases, kernel_cases
 from tests.gemm_variant_cases import ALIGNMENT_TESTED, CASES, INSTANTIATED, THRESHOLDS, UNREACHABLE, case_id, derived, model, model_variant
 from tests.test_elementwise_host import CSRC, _reported_names
 
 ALL_CASES = kernel_cases.CASES + CASES
+VARIANT_CASES = CASES + grad_cases.CASES             # every table that holds a variant of libmbnb_hip's record
+ALL_UNREACHABLE = UNREACHABLE | grad_cases.UNREACHABLE
 LAUNCHER_FILES = ("matmul4_kernels.hip", "int8_kernels.hip", "gemm_dense.hip", "gemm_small.hip", "gemm_small8.hip", "gemm_mid.hip",
                   "gemm_fused4.hip", "gemm_f32.hip", "nn_kernels.hip")
 
@@ -52,6 +55,8 @@ def _alternatives(arg):
     m = re.fullmatch(r'[^?]+\?\s*(-?\d+|"[^"]*")\s*:\s*(-?\d+|"[^"]*")', arg)
     if m:
         return [re.escape(m.group(1).strip('"')), re.escape(m.group(2).strip('"'))]
+    if re.fullmatch(r'(?:[^?"]+\?\s*"[^"]*"\s*:\s*)+"[^"]*"', arg):               # a chain: c1 ? "a" : c2 ? "b" : "c"
+        return [re.escape(lit) for lit in re.findall(r'"([^"]*)"', arg)]
     return [r"\d+"]
 
 
@@ -107,18 +112,25 @@ def test_the_variant_scan_sees_the_library():
             r"i8_dense\ OUTL2\ NCH2", r"generic\ ROWS8\ flags\d+", r"gemm256p\ am4", "gemm256", "fused4", r"skinny8\ MT4"} <= pats, sorted(pats)
     assert len([p for p in pats if p.startswith("gemv_lean")]) == 6 and len([p for p in pats if p.startswith(r"gemv\ MT")]) == 14
     assert len([p for p in pats if p.startswith(r"small\ MF")]) == 5 and len([p for p in pats if p.startswith("dense_nb")]) == 3
+    # the gradient path: format x T x nested | plain x vec | scalar of the pass, format x T x O x nested | plain of the generic kernel
+    assert len([p for p in pats if p.startswith(r"grad_t\ ")]) == 5 * 2 * 2 * 2 and len([p for p in pats if p.startswith(r"grad_generic\ ")]) == 5 * 3 * 3 * 2
+    assert re.escape("grad_t fp8 bf16 plain scalar") in pats and re.escape("grad_generic dense f32>f16 plain") in pats
 
 
 # ----------------------------------------------------------------------------------------------- closure over the variants
 def test_every_variant_the_sources_report_has_a_case_and_no_case_names_another():
     pats = reported_variants()
-    have = {c["variant"] for c in CASES}
-    uncovered = sorted(p for p in pats if not any(re.fullmatch(p, v) for v in have) and p not in {re.escape(u) for u in UNREACHABLE})
-    assert uncovered == [], "a launcher reports a variant that no case of tests/gemm_variant_cases.py takes"
+    have = {c["variant"] for c in VARIANT_CASES}
+    uncovered = sorted(p for p in pats if not any(re.fullmatch(p, v) for v in have) and p not in {re.escape(u) for u in ALL_UNREACHABLE})
+    assert uncovered == [], "a launcher reports a variant that no case of tests/gemm_variant_cases.py or tests/grad_cases.py takes"
     strangers = sorted(v for v in have if v and not any(re.fullmatch(p, v) for p in pats))
     assert strangers == [], "a case names a variant the launchers never report"
-    for u in UNREACHABLE:
+    for u in ALL_UNREACHABLE:
         assert re.escape(u) in pats and u not in have, u
+    # the GEMM tables alone are closed over everything but the gradient path's variants, as before
+    gemm = {c["variant"] for c in CASES}
+    assert all(p.startswith(("grad_t\\ ", "grad_generic\\ ")) for p in pats if not any(re.fullmatch(p, v) for v in gemm) and p not in {re.escape(u) for u in UNREACHABLE})
+    assert not any(v.startswith(("grad_t ", "grad_generic ")) for v in gemm)
 
 
 def test_every_case_takes_the_name_and_the_variant_the_launchers_conditions_give():
