@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _group_native, _lora_native, _native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -634,13 +634,13 @@ def matmul_fp4(input: Tensor, weight_packed: Tensor, weight_state: QuantState,
     return matmul_4bit(input, weight_packed, weight_state, bias)
 
 
-def _group_rows(A: Tensor, weights, biases, compute_dtype: Optional[torch.dtype]):
+def _group_rows(A: Tensor, weights, biases, compute_dtype: Optional[torch.dtype], max_rows: int = 1):
     """What the fused launch of matmul_4bit_grouped needs -- (K, quant_type, blocksize, w_dtype, [(packed, desc, bias, N), ...], keep) --
-    or None where the call is not one row times weights of one format (or where a member would not pass matmul_4bit's own checks:
-    the member-by-member path then raises what matmul_4bit raises).  Whether the kernel takes the shapes is the library's decision."""
+    or None where the call is not 1 ... `max_rows` rows times weights of one format (or where a member would not pass matmul_4bit's own
+    checks: the member-by-member path then raises what matmul_4bit raises).  Whether the kernel takes the shapes is the library's decision."""
     if torch.is_grad_enabled() and (A.requires_grad or any(b is not None and b.requires_grad for b in biases)):
         return None
-    if A.device.type != 'cuda' or A.dim() == 0 or A.shape[-1] == 0 or A.numel() != A.shape[-1]:
+    if A.device.type != 'cuda' or A.dim() == 0 or A.shape[-1] == 0 or not 0 < A.numel() <= max_rows * A.shape[-1]:
         return None
     K = int(A.shape[-1])
     first = weights[0][1]
@@ -677,21 +677,27 @@ def matmul_4bit_grouped(
 ) -> Tuple[Tensor, ...]:
     """
     ``tuple(matmul_4bit(A, packed, state, bias, compute_dtype) for (packed, state), bias in zip(weights, biases))`` -- the same
-    values bit for bit, the same errors -- with ONE kernel launch per 16 members where A is a single row (the decode step of a
-    transformer block: q / k / v share their input, and so do gate / up).
+    values bit for bit, the same errors -- with ONE kernel launch per 16 members where A folds to 1 ... 16 rows (the decode step of a
+    transformer block, alone or in a served batch: q / k / v share their input, and so do gate / up).
 
     `weights` is a sequence of ``(packed, QuantState)`` pairs, `biases` one Tensor or None per member (default: no bias).
     An empty sequence returns ``()``.
 
-    The fused launch (libmbnb_group.so, k_gemv4_group: the row body of matmul_4bit's own M = 1 kernel behind a member table)
-    serves a call in which A folds to one row, no gradient is wanted, every member has the same quant_type, blocksize and
-    weight dtype, and the output dtype equals the weight dtype; the library then decides on the shapes (blocksize 64, K a
-    multiple of 64 in 1024 ... 16384, 16-bit dtype, aligned operands, all absmax plain or all double-quantised) and a chunk it
-    declines runs member by member.  Everything else -- more rows, a gradient (differentiable through matmul_4bit's autograd
-    function), mixed formats, f32 weights, another compute_dtype -- is the member-by-member loop above.
+    The fused launches serve a call in which A folds to 1 ... 16 rows, no gradient is wanted, every member has the same quant_type,
+    blocksize and weight dtype, and the output dtype equals the weight dtype; the library then decides on the shapes, and a chunk
+    it declines runs member by member:
 
-    On the fused path the outputs are VIEWS of one allocation of sum(N) elements: writing to one in place never touches another,
-    but each keeps the whole allocation alive.
+    - one row: libmbnb_group.so, k_gemv4_group -- the row body of matmul_4bit's own M = 1 kernel behind a member table (blocksize
+      64, K a multiple of 64 in 1024 ... 16384, 16-bit dtype, aligned operands, all absmax plain or all double-quantised);
+    - 2 ... 16 rows: libmbnb_batch.so, k_skinny4_group -- the workgroup of matmul_4bit's own weight-streaming MFMA kernel for these
+      row counts behind the same table (blocksize a power of two >= 32, K a multiple of 128 and of the blocksize in 128 ... 16384,
+      16-bit dtype, aligned operands, all absmax plain or all double-quantised).
+
+    Everything else -- 17 rows or more, a gradient (differentiable through matmul_4bit's autograd function), mixed formats, f32
+    weights, another compute_dtype -- is the member-by-member loop above.
+
+    On the fused paths the outputs are VIEWS of one allocation of rows * sum(N) elements, each member's a dense [rows, N] block:
+    writing to one in place never touches another, but each keeps the whole allocation alive.
     """
     weights = list(weights)
     biases = [None] * len(weights) if biases is None else list(biases)
@@ -699,13 +705,17 @@ def matmul_4bit_grouped(
         raise ValueError(f"matmul_4bit_grouped: {len(weights)} weights but {len(biases)} biases")
     if not weights:
         return ()
-    plan = _group_rows(A, weights, biases, compute_dtype)
+    plan = _group_rows(A, weights, biases, compute_dtype, _batch_native.MAX_M)
     if plan is None:
         return tuple(matmul_4bit(A, B, state, bias, compute_dtype) for (B, state), bias in zip(weights, biases))
     K, qt, blocksize, w_dtype, rows, keep = plan
-    x, table, outs = _group_table(A, K, w_dtype, rows)
+    M = A.numel() // K
+    x, table, outs = _group_table(A, K, w_dtype, rows, M)
     with on_device(A.device):
-        launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+        if M == 1:
+            launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+        else:
+            launched = _batch_native.gemm4(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
     for c, ok in enumerate(launched):
         if not ok:    # the library declined this chunk before launching anything: its members one by one
             for i in range(c * _group_native.MAX_MEMBERS, min((c + 1) * _group_native.MAX_MEMBERS, len(rows))):
@@ -713,18 +723,19 @@ def matmul_4bit_grouped(
     return tuple(outs)
 
 
-def _group_table(A: Tensor, K: int, w_dtype: torch.dtype, rows):
+def _group_table(A: Tensor, K: int, w_dtype: torch.dtype, rows, M: int = 1):
     """(x, table, outs) of a fused grouped launch over _group_rows' `rows`: A prepared once for all members (matmul_4bit: A.to(weight
-    dtype), contiguous), the Member field tuples, and the outputs -- views of ONE allocation of sum(N) elements."""
-    x = _as(A.reshape(1, K), w_dtype)
-    out = torch.empty(sum(r[3] for r in rows), dtype=w_dtype, device=A.device)
+    dtype), contiguous [M, K]), the Member field tuples, and the outputs -- views of ONE allocation of M * sum(N) elements, member g's
+    the dense [M, N_g] block."""
+    x = _as(A.reshape(M, K), w_dtype)
+    out = torch.empty(M * sum(r[3] for r in rows), dtype=w_dtype, device=A.device)
     table, outs, first = [], [], out.data_ptr()
     esize, o = out.element_size(), 0
     for B, desc, bias, N in rows:
         table.append((B.data_ptr(), desc.absmax_f32 or 0, desc.absmax_i8 or 0, desc.absmax2 or 0,
                       0 if bias is None else bias.data_ptr(), first + o * esize, N, desc.blocksize2, 0))
-        outs.append(out[o:o + N].view(*A.shape[:-1], N))
-        o += N
+        outs.append(out[o:o + M * N].view(*A.shape[:-1], N))
+        o += M * N
     return x, table, outs
 
 
@@ -779,16 +790,24 @@ def matmul_4bit_lora_grouped(
     elementwise bounds of DESIGN.md 17 around the float64 value of the expression above, on whichever path computed it.  A member
     whose adapter is ``None`` equals `matmul_4bit` bit for bit on every path.
 
-    The fused path (libmbnb_lora.so) makes TWO launches per 16 members: `k_lora_down` (t = lora_A . x in f32 for every adapter row of
-    every member) and `k_gemv4_group_lora` (the grouped GEMV's rows, each adding ``scaling * lora_B[n, :] . t`` to its f32 accumulator
-    before the bias and the one rounding).  It serves a call that `matmul_4bit_grouped` would fuse (A folds to one row, no gradient
-    wanted, one quant_type / blocksize / weight dtype, output dtype = weight dtype) in which every adapter tensor is on A's device,
-    in the weight dtype, contiguous, shaped ``[r, K]`` / ``[N, r]`` and wants no gradient; the library then decides on the shapes
-    (those of the grouped GEMV, and 1 <= r <= 256 with aligned operands), and a chunk it declines runs through the composed form.
-    The outputs are views of one allocation, the f32 workspaces slices of another.
+    The bound holds on three paths.  Two are fused and make TWO launches per 16 members, the down-projections t = A . lora_A^T in f32
+    for every adapter row of every member, then the grouped base launch whose elements add ``scaling * lora_B[n, :] . t[m, :]`` to
+    their f32 sum before the bias and the one rounding:
 
-    Everything else -- more rows, a wanted gradient, mixed formats, r > 256, another dtype -- runs ONE composed form per member:
-    `matmul_4bit` (this library's HIP kernels, differentiable in A and the bias) plus
+    - A folds to one row: libmbnb_lora.so, `k_lora_down` and `k_gemv4_group_lora`;
+    - A folds to 2 ... 16 rows: libmbnb_batch.so, `k_lora_down_rows` and `k_skinny4_group` with its rank-r epilogue.  Every row of
+      the batch uses the member's one adapter; a different adapter per row is not part of this function.  For these row counts
+      the value's bits differ from the releases that ran the composed form here -- one rounding to the weight dtype instead of
+      five -- which is inside the contract above, not outside it.
+
+    They serve a call that `matmul_4bit_grouped` would fuse (1 ... 16 rows, no gradient wanted, one quant_type / blocksize / weight
+    dtype, output dtype = weight dtype) in which every adapter tensor is on A's device, in the weight dtype, contiguous, shaped
+    ``[r, K]`` / ``[N, r]`` and wants no gradient; the library then decides on the shapes (those of the grouped launch for that
+    row count, and 1 <= r <= 256 with aligned operands), and a chunk it declines runs through the composed form.  The outputs are
+    views of one allocation, the f32 workspaces slices of another.
+
+    Everything else -- 17 rows or more, a wanted gradient, mixed formats, r > 256, another dtype -- runs ONE composed form per
+    member: `matmul_4bit` (this library's HIP kernels, differentiable in A and the bias) plus
     ``((A.to(T) @ lora_A.t()) @ lora_B.t()) * scaling`` in torch ops.  That half is torch's GEMM, NOT a HIP kernel of this library;
     autograd gives lora_A, lora_B and A their gradients through it.  An efficient adapter path for prefill and training is not
     part of this function.
@@ -805,22 +824,26 @@ def matmul_4bit_lora_grouped(
     def composed(i):
         return _lora_composed(A, weights[i][0], weights[i][1], biases[i], adapters[i], compute_dtype)
 
-    plan = _group_rows(A, weights, biases, compute_dtype)
+    plan = _group_rows(A, weights, biases, compute_dtype, _batch_native.MAX_M)
     ranks = None if plan is None else _lora_ranks(A, plan[0], plan[3], plan[4], adapters)
     if ranks is None:
         return tuple(composed(i) for i in range(len(weights)))
     K, qt, blocksize, w_dtype, rows, keep = plan
-    x, table, outs = _group_table(A, K, w_dtype, rows)
-    t = torch.empty(sum(r[2] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
+    M = A.numel() // K
+    x, table, outs = _group_table(A, K, w_dtype, rows, M)
+    t = torch.empty(M * sum(r[2] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
     rank_table, t0, o = [], t.data_ptr(), 0
     for r in ranks:
         if r is None:
             rank_table.append(_lora_native.NO_ADAPTER)
         else:
-            rank_table.append((r[0].data_ptr(), r[1].data_ptr(), t0 + 4 * o, r[2], r[3]))
-            o += r[2]
+            rank_table.append((r[0].data_ptr(), r[1].data_ptr(), t0 + 4 * o, r[2], r[3]))      # t: the f32 [M, R] block of this member
+            o += M * r[2]
     with on_device(A.device):
-        launched = _lora_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
+        if M == 1:
+            launched = _lora_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
+        else:
+            launched = _batch_native.gemm4_lora(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
     for c, ok in enumerate(launched):
         if not ok:    # the library declined this chunk before launching anything: its members in the composed form
             for i in range(c * _lora_native.MAX_MEMBERS, min((c + 1) * _lora_native.MAX_MEMBERS, len(rows))):

@@ -3,8 +3,8 @@ Linear4bitGroup — several Linear4bit layers that are handed the same input (q 
 
 No counterpart in the reference, whose layers run one at a time.  The members stay ordinary Linear4bit modules in an
 nn.ModuleList, so their state-dict keys are their own under ``layers.<i>.``; the forward is
-`functional.matmul_4bit_grouped`: one kernel launch for a single row of input (a decode step), the layers one by one for
-everything else, with each layer's own result bit for bit either way.
+`functional.matmul_4bit_grouped`: one kernel launch for 1 to 16 rows of input (a decode step, alone or in a served batch), the
+layers one by one for everything else, with each layer's own result bit for bit either way.
 """
 from typing import Sequence, Tuple
 

@@ -4,7 +4,7 @@ Linear4bitLoRA / Linear4bitLoRAGroup — Linear4bit layers with un-merged LoRA a
 No counterpart in the reference.  A LoRA trained over a 4-bit base cannot be merged into it without re-quantising, so the layer
 that was trained is the layer that decodes: ``base(x) + scaling * (x @ lora_A^T) @ lora_B^T``.  The base stays an ordinary
 Linear4bit submodule (its state-dict keys are its own under ``base.``); the forward is `functional.matmul_4bit_lora_grouped`: two
-kernel launches for a single row of input under `no_grad` / `inference_mode` (the adapters are parameters), and the composed form --
+kernel launches for 1 to 16 rows of input under `no_grad` / `inference_mode` (the adapters are parameters), and the composed form --
 `matmul_4bit` plus the adapter in torch ops, differentiable in the adapters and the input -- for everything else.
 """
 import math
