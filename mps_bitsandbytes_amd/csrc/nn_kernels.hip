@@ -312,7 +312,8 @@ __global__ __launch_bounds__(256) void k_outlier_add(const T *__restrict__ X, in
             {
                 const int i = threadIdx.x / CH, j = threadIdx.x % CH;   // 256 threads = RM x CH values
                 const int64_t m = m0 + i;
-                xs[i][j] = (m < M && j0 + j < n_out) ? to_f32(X[m * K + oidx[j0 + j]]) : 0.0f;
+                const int64_t c = (m < M && j0 + j < n_out) ? oidx[j0 + j] : -1;   // an index outside [0, K) contributes zero, as in
+                xs[i][j] = (c >= 0 && c < K) ? to_f32(X[m * K + c]) : 0.0f;         // the mask and the compact activations above
             }
             __syncthreads();
             float w[CN][CH];

@@ -1634,6 +1634,8 @@ def outlier_linear(input: Tensor, weight_int8: Tensor, weight_scales: Tensor, ou
     non-outlier input columns, int8 x int8 contraction on the MFMA, the outlier columns in `dtype`, bias.
     The reference multiplies dtype-rounded dequantised operands; the exact integer contraction used here differs
     from it by <= 4e-4 (fp16) / 1.3e-3 (bf16) relative (Frobenius).
+    An entry of `outlier_indices` outside ``[0, in_features)`` is not range-checked on the host (no device
+    synchronisation): on every path it masks no column and its column of `outlier_weights` contributes zero.
     """
     _check_device(input, "outlier_linear")
     _check_device(weight_int8, "outlier_linear")

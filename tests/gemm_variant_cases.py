@@ -813,7 +813,8 @@ OPERAND_ALIGNMENT_TESTED = {
 
 # change detectors (tests/test_gemm_variants_host.py): the pointer tests (aligned16 / reinterpret_cast<uintptr_t>) of every GEMM launcher
 # file, and the integer literals its code compares M, N, K, K_weight, a tile, step or workgroup count, N * K or M * N with.  One that is
-# added or removed breaks the count until THRESHOLDS / ALIGNMENT_TESTED and their cases follow.
+# added or removed breaks the count until THRESHOLDS / ALIGNMENT_TESTED and their cases follow.  nn_kernels.hip's seven pointer tests and
+# its other limits each have a pair of cases in tests/nn_cases.py (ALIGNMENT_TESTED and THRESHOLDS there).
 ALIGNMENT_TEST_COUNTS = {"matmul4_kernels.hip": 13, "int8_kernels.hip": 17, "gemm_dense.hip": 6, "gemm_small.hip": 1, "gemm_small8.hip": 3,
                          "gemm_mid.hip": 1, "gemm_fused4.hip": 5, "gemm_f32.hip": 2, "nn_kernels.hip": 7}
 INTEGER_LIMITS = {

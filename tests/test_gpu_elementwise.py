@@ -310,6 +310,40 @@ def _run_outlier(c):
     return kern, assert_bound_elementwise(y, ref, bound, kern, "outlier_linear")
 
 
+def outlier_masked_bound(x, Wd, pos, ow, b, ref, dt):
+    """The per-element bound of tests/test_gpu_nn_forms.py around oracle.outlier_linear: _run_outlier's terms, with the quantisation
+    step taken from the row maximum over the KEPT columns and the outlier columns entering S through `ow` without a step.
+
+    x [M, K] in dt, Wd [N, K] the oracle's decode of the int8 weight, pos the outlier columns, ow [N, len(pos)], b [N] or None, ref
+    [M, N]; all on one device, the result float64.  With kept = the columns outside pos, m_i = max(max_kept |x_ik|, 1e-8) and
+    step_i = m_i / 127 (quantize_rowwise's scale of the masked row: an outlier column neither sets it nor is quantised),
+
+        S_in = sum_kept (|x_ik| + step_i) |Wd_nk| + sum_pos |x_ij| |ow_nj| + |b_n|
+
+    bounds the magnitude of every partial result on either side: a kept activation is replaced by its code times step_i, at most step_i
+    away; an outlier activation is used as it is.  Both sides quantise alike; the kernel contracts the integers exactly and scales once in
+    f32, the oracle multiplies the two decoded operands rounded to dt and accumulates in f32.  So: the two operand roundings cost 2 u S,
+    the accumulation and the f32 scaling g S with g = (K + 2) 2^-23, and the roundings of the two partial sums (the int8 product and the
+    outlier term), done on both sides over values that differ by no more than the above, one more u S; the two last roundings (the sum of
+    the partial sums, then the bias) act on values within that of ref: 2 u |ref| on each side.  One int8 step of x on one element of the
+    row (a tie quantised the other way) adds step_i max_kept |Wd_nk|; half of f16's smallest subnormal covers a result rounded there.
+    With the step taken over the full row instead, the x64 outlier columns would loosen the first and the last term 64-fold."""
+    K = x.shape[1]
+    dev = x.device
+    keep = torch.ones(K, dtype=torch.bool, device=dev)
+    keep[torch.as_tensor(pos, dtype=torch.int64, device=dev)] = False
+    xd, Wk = x.double(), Wd.double().abs() * keep.double()[None, :]
+    step = (xd.abs() * keep.double()[None, :]).amax(1, keepdim=True).clamp_min(1e-8) / 127.0
+    S = ((xd.abs() + step) * keep.double()[None, :]) @ Wk.t()
+    if len(pos):
+        S = S + xd[:, torch.as_tensor(pos, dtype=torch.int64, device=dev)].abs() @ ow.double().abs().t()
+    if b is not None:
+        S = S + b.double().abs()[None, :]
+    u = UNIT[dt]
+    g = (K + 2) * 2.0 ** -23
+    return 4 * u * ref.double().abs() + (3 * u + g) * S + step * Wk.amax(1)[None, :] + (2.0 ** -24 if dt == torch.float16 else 0.0)
+
+
 def _run_embedding(c):
     M, dim, num, dt = c["M"], c["N"], c["K"], DT[c["dt"]]
     idx = torch.from_numpy((synthetic.uniform_u64(M, seed=71) % np.uint64(num)).astype(np.int64))
