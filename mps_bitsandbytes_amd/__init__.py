@@ -14,6 +14,7 @@ __version__ = "0.1.0"
 from .functional import (
     QuantState,
     quantize_4bit, dequantize_4bit, matmul_4bit, matmul_4bit_grouped, matmul_4bit_lora_grouped,
+    matmul_4bit_multilora_grouped,
     quantize_nf4, dequantize_nf4, matmul_nf4, NF4_CODEBOOK, create_normal_map,
     quantize_fp4, dequantize_fp4, matmul_fp4, FP4_CODEBOOK, create_fp4_map,
     quantize_blockwise, dequantize_blockwise,
@@ -25,7 +26,7 @@ from .functional import (
     sparse_coo_from_dense, quantize_sparse_coo, spmm_coo, spmm_coo_int8,
 )
 from .nn import (Linear4bit, Linear4bitGroup, Linear4bitLoRA, Linear4bitLoRAGroup, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
-                 OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback)
+                 OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup)
 from .optim import (Adam8bit, AdamW8bit, Lion8bit, SGD8bit, PagedAdam, PagedAdamW, PagedLion,
                     quantize_state, dequantize_state)
 from .integration import (
@@ -63,4 +64,5 @@ __all__ = [
     'BitsAndBytesConfig', 'quantize_model', 'replace_linear_with_4bit', 'replace_linear_with_8bit', 'get_memory_footprint',
     'matmul_4bit_grouped', 'Linear4bitGroup',
     'matmul_4bit_lora_grouped', 'Linear4bitLoRA', 'Linear4bitLoRAGroup',
+    'matmul_4bit_multilora_grouped', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup',
 ]

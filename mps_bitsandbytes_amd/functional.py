@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -847,6 +847,122 @@ def matmul_4bit_lora_grouped(
     for c, ok in enumerate(launched):
         if not ok:    # the library declined this chunk before launching anything: its members in the composed form
             for i in range(c * _lora_native.MAX_MEMBERS, min((c + 1) * _lora_native.MAX_MEMBERS, len(rows))):
+                outs[i] = composed(i)
+    return tuple(outs)
+
+
+def _multilora_ranks(A: Tensor, K: int, w_dtype: torch.dtype, rows, banks):
+    """One (lora_A, lora_B, scaling, R, S) or None per member where the fused per-row adapter launch can take the banks as they are --
+    every tensor on A's device and contiguous, lora_A [S, R, K] and lora_B [S, N, R] in the weight dtype, scaling f32 [S], R <= 64, no
+    gradient wanted -- else None.  The alignment is the library's decision."""
+    ranks = []
+    for (_, _, _, N), bank in zip(rows, banks):
+        if bank is None:
+            ranks.append(None)
+            continue
+        lora_A, lora_B, scaling = bank
+        S, R = (int(lora_A.shape[0]), int(lora_A.shape[1])) if lora_A.dim() == 3 else (-1, -1)
+        for t, dtype, shape in ((lora_A, w_dtype, (S, R, K)), (lora_B, w_dtype, (S, N, R)), (scaling, torch.float32, (S,))):
+            if (t.device != A.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                    or (t.requires_grad and torch.is_grad_enabled())):
+                return None
+        if R > _mlora_native.MAX_R:
+            return None
+        ranks.append((lora_A, lora_B, scaling, R, S) if R > 0 and S > 0 else None)
+    return ranks
+
+
+def _multilora_composed(A: Tensor, B: Tensor, state: QuantState, bias: Optional[Tensor], bank, ids: Tensor,
+                        compute_dtype: Optional[torch.dtype]) -> Tensor:
+    """One member of matmul_4bit_multilora_grouped in its composed form: matmul_4bit (HIP kernels, differentiable in A and the bias),
+    then one slot after the other in torch ops, each selected by row with `where` -- a row without an adapter keeps matmul_4bit's
+    bits, and what an unselected slot holds (a NaN included) never reaches a row.  The ids stay on the device."""
+    y = matmul_4bit(A, B, state, bias, compute_dtype)
+    if bank is None:
+        return y
+    lora_A, lora_B, scaling = bank
+    x = A if A.dtype == state.dtype else A.to(state.dtype)        # the rows as matmul_4bit feeds them
+    if x.dtype != lora_A.dtype:
+        x = x.to(lora_A.dtype)
+    for s in range(int(lora_A.shape[0])):
+        u = ((x @ lora_A[s].t()) @ lora_B[s].t()) * scaling[s]        # a 0-dim f32 factor: u keeps its dtype
+        y = torch.where((ids == s).unsqueeze(-1), y + (u if u.dtype == y.dtype else u.to(y.dtype)), y)
+    return y
+
+
+def matmul_4bit_multilora_grouped(
+    A: Tensor,
+    weights: Sequence[Tuple[Tensor, QuantState]],
+    banks: Sequence[Optional[Tuple[Tensor, Tensor, Tensor]]],
+    adapter_ids: Tensor,
+    biases: Optional[Sequence[Optional[Tensor]]] = None,
+    compute_dtype: Optional[torch.dtype] = None,
+) -> Tuple[Tensor, ...]:
+    """
+    `matmul_4bit_lora_grouped` for a served batch whose rows carry DIFFERENT un-merged adapters (continuous batching over one frozen
+    4-bit base): per member and row m, with ``s = adapter_ids[m]``,
+    ``A[m] @ dequant(W)^T + bias + scaling[s] * (A[m] @ lora_A[s]^T) @ lora_B[s]^T``.
+
+    `banks` holds one entry per member: ``None`` or ``(lora_A [S, r, K], lora_B [S, N, r], scaling)`` with `scaling` an f32 ``[S]``
+    tensor on A's device; S must be equal across the banks.  `adapter_ids` is an integer tensor of shape ``A.shape[:-1]`` on A's
+    device.  A row whose id lies outside ``[0, S)`` -- -1, S, anything else -- uses NO adapter: its values are `matmul_4bit`'s bit for
+    bit on every path (out-of-range ids are skipped, as `spmm_coo` skips them: a check that raises would synchronise).  The ids are
+    never read on the host.  An int32 contiguous tensor is passed to the kernels as it is, so a caller may overwrite it in place
+    between the replays of a captured graph; anything else is converted once per call.  With every bank ``None`` the call IS
+    `matmul_4bit_grouped`.
+
+    What is promised is the BOUND of `matmul_4bit_lora_grouped` around the float64 value formed with each row's adapter.  Two paths:
+
+    - A folds to 2 ... 16 rows in a call `matmul_4bit_grouped` would fuse, every bank tensor is in the weight dtype (the scaling in
+      f32), contiguous, on A's device, r <= 64, and no gradient is wanted: libmbnb_mlora.so, TWO launches per 16 members --
+      `k_lora_down_sel` (t[m] = lora_A[s] . A[m] in f32) and `k_skinny4_mlora`, the grouped base launch with a per-row rank-r
+      epilogue.  Row m then equals, bit for bit, row m of `matmul_4bit_lora_grouped` on its 2 ... 16 row path with the adapters
+      ``(lora_A[s], lora_B[s], float(scaling[s]))``.  The library decides on shapes and alignment; a chunk it declines runs composed.
+    - Everything else -- 1 row, 17 rows or more, r > 64, a wanted gradient, mixed formats, an f32 bank -- runs the composed form per
+      member: `matmul_4bit`, then per slot ``torch.where(ids == s, y + ((x @ lora_A[s].t()) @ lora_B[s].t()) * scaling[s], y)``:
+      sync-free, differentiable in A, the bias and the bank, and S small torch GEMMs over all rows per member.
+    """
+    weights, banks = list(weights), list(banks)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    if len(biases) != len(weights):
+        raise ValueError(f"matmul_4bit_multilora_grouped: {len(weights)} weights but {len(biases)} biases")
+    if len(banks) != len(weights):
+        raise ValueError(f"matmul_4bit_multilora_grouped: {len(weights)} weights but {len(banks)} banks")
+    if all(bank is None for bank in banks):
+        return matmul_4bit_grouped(A, weights, biases, compute_dtype)
+    slots = {int(bank[0].shape[0]) for bank in banks if bank is not None}
+    if len(slots) != 1:
+        raise ValueError(f"matmul_4bit_multilora_grouped: the banks hold {sorted(slots)} adapters; one S for all banks is needed")
+    if tuple(adapter_ids.shape) != tuple(A.shape[:-1]):
+        raise ValueError(f"matmul_4bit_multilora_grouped: adapter_ids has shape {tuple(adapter_ids.shape)}, A has rows {tuple(A.shape[:-1])}")
+    if adapter_ids.dtype.is_floating_point or adapter_ids.dtype.is_complex or adapter_ids.dtype == torch.bool:
+        raise TypeError(f"matmul_4bit_multilora_grouped: adapter_ids must be an integer tensor, got {adapter_ids.dtype}")
+
+    def composed(i):
+        return _multilora_composed(A, weights[i][0], weights[i][1], biases[i], banks[i], adapter_ids, compute_dtype)
+
+    plan = _group_rows(A, weights, biases, compute_dtype, _mlora_native.MAX_M)
+    M = 0 if plan is None else A.numel() // plan[0]
+    ranks = None if plan is None or M < _mlora_native.MIN_M or adapter_ids.device != A.device else \
+        _multilora_ranks(A, plan[0], plan[3], plan[4], banks)
+    if ranks is None:
+        return tuple(composed(i) for i in range(len(weights)))
+    K, qt, blocksize, w_dtype, rows, keep = plan
+    ids = adapter_ids if adapter_ids.dtype == torch.int32 and adapter_ids.is_contiguous() else adapter_ids.to(torch.int32).contiguous()
+    x, table, outs = _group_table(A, K, w_dtype, rows, M)
+    t = torch.empty(M * sum(r[3] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
+    bank_table, t0, o = [], t.data_ptr(), 0
+    for r in ranks:
+        if r is None:
+            bank_table.append(_mlora_native.NO_BANK)
+        else:
+            bank_table.append((r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(), t0 + 4 * o, r[3], r[4]))      # t: the f32 [M, R] block of this member
+            o += M * r[3]
+    with on_device(A.device):
+        launched = _mlora_native.gemm4(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, bank_table, ids.data_ptr(), stream_ptr(A.device))
+    for c, ok in enumerate(launched):
+        if not ok:    # the library declined this chunk before launching anything: its members in the composed form
+            for i in range(c * _mlora_native.MAX_MEMBERS, min((c + 1) * _mlora_native.MAX_MEMBERS, len(rows))):
                 outs[i] = composed(i)
     return tuple(outs)
 
