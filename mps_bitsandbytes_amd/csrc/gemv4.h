@@ -34,7 +34,9 @@ template <> struct Dot2<bf16_t> {
 };
 
 // KU k-steps of 2048 (64 lanes x 32 k) are processed per loop trip with ALL their loads issued
-// before the first use; out-of-range chunks load from a clamped address with a zeroed absmax
+// before the first use; out-of-range chunks load from a clamped address and are contracted like any
+// other, and the lane then keeps the sums it had before the chunk: whatever was loaded -- an Inf
+// activation, a NaN absmax, which a zeroed weight would turn into NaN -- contributes nothing
 // (no branch or select between a load and its use: that makes hipcc wait vmcnt(0) per load).
 // DEC (decode flavour): 0 = 16-entry f32 table, one ds_read_b32 per nibble (v_bfe offsets), v_pk_mul_f32;
 // 1 = 256-entry byte table of (code[b & 15], code[b >> 4]) pairs, one ds_read_b64 per packed byte, v_pk_mul_f32;
@@ -83,18 +85,16 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
     // The packed weights and absmax of trip t+1 are requested before trip t is decoded, and those of trip 0
     // before the prologue (code table, activation staging, barrier): HBM latency overlaps the prologue.
     // K % 32 == 0 here, so a lane's 32-k chunk is entirely inside or outside [0, K).  Outside: load from
-    // k = 0 (in bounds) and zero the absmax, so the products vanish -- no branch, no select between a load
-    // and its use.
+    // k = 0 (in bounds), decode and contract as usual, and select the accumulators saved before the chunk
+    // once it is done (`keep` below) -- no branch, no select between a load and its use, and nothing of
+    // chunk 0 (an Inf activation, a NaN absmax) reaches the sum.  Inside, the chain of adds is untouched.
     u32x4 wq[KU][NR], wq_n[KU][NR];
     float a[KU][NR], a_n[KU][NR];
-    float vf[KU], vf_n[KU];
     auto request_w = [&](int64_t kbase) {
 #pragma unroll
         for (int u = 0; u < KU; u++) {
             const int64_t k0 = kbase + u * 2048 + lane * 32;
-            const bool wvalid = k0 < K;
-            const int64_t kc = wvalid ? k0 : 0;
-            vf_n[u] = wvalid ? 1.0f : 0.0f;
+            const int64_t kc = k0 < K ? k0 : 0;
 #pragma unroll
             for (int r = 0; r < NR; r++) {
                 wq_n[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(wrow[r] + (kc >> 1)));
@@ -145,9 +145,9 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
         u32x4 xv[XLDS ? 1 : KU][XLDS ? 1 : MT][4];
         u32x4 xq[2][MT];
         int64_t kcs[KU];
+        bool inside[KU];
 #pragma unroll
         for (int u = 0; u < KU; u++) {
-            vf[u] = vf_n[u];
 #pragma unroll
             for (int r = 0; r < NR; r++) {
                 wq[u][r] = wq_n[u][r];
@@ -160,6 +160,7 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
             const int64_t k0 = kbase + u * 2048 + lane * 32;
             const int64_t kc = k0 < K ? k0 : 0;
             kcs[u] = kc;
+            inside[u] = k0 < K;
             if constexpr (!XLDS) {
 #pragma unroll
                 for (int c = 0; c < 4; c++)
@@ -169,14 +170,11 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
         }
         // keep every load above issued before anything waits on one of them
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < KU; u++)
-#pragma unroll
-            for (int r = 0; r < NR; r++) a[u][r] *= vf[u];
         // Decode, software-pipelined over the KU*NR*4 quarters (8 k each): the table lookups of quarter q+1
         // are issued before quarter q is multiplied, so their LDS latency is not waited for in place.
         constexpr int NQ = KU * NR * 4;
         float L[2][8];
+        float keep[NR][MT];
         auto lookup = [&](auto qq, float (&Lq)[8]) {
             constexpr int q = decltype(qq)::value;
             constexpr int u = q / (NR * 4), r = (q / 4) % NR, c = q % 4;
@@ -209,6 +207,12 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
         auto consume = [&](auto qq, const float (&Lq)[8]) {
             constexpr int q = decltype(qq)::value;
             constexpr int u = q / (NR * 4), r = (q / 4) % NR, c = q % 4;
+            if constexpr (q % (NR * 4) == 0) {      // the first quarter of chunk u
+#pragma unroll
+                for (int rr = 0; rr < NR; rr++)
+#pragma unroll
+                    for (int i = 0; i < MT; i++) keep[rr][i] = acc[rr][i];
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 uint32_t wp;
@@ -226,6 +230,12 @@ __global__ __launch_bounds__(256) void k_gemv4(const T *__restrict__ X, const ui
                     if constexpr (XLDS) acc[r][i] = Dot2<T>::run(wp, xq[q & 1][i][j], acc[r][i]);
                     else acc[r][i] = Dot2<T>::run(wp, xv[u][i][c][j], acc[r][i]);
                 }
+            }
+            if constexpr (q % (NR * 4) == NR * 4 - 1) {      // the last quarter of chunk u: a chunk past K leaves the sums as they were
+#pragma unroll
+                for (int rr = 0; rr < NR; rr++)
+#pragma unroll
+                    for (int i = 0; i < MT; i++) acc[rr][i] = inside[u] ? acc[rr][i] : keep[rr][i];
             }
         };
         lookup(std::integral_constant<int, 0>{}, L[0]);

@@ -27,9 +27,11 @@ from mps_bitsandbytes_amd import _native
 from mps_bitsandbytes_amd import functional as F
 from tests import batch_cases as bc
 from tests import lora_cases as lc
+from tests import nonfinite
 from tests.elementwise import assert_linear_elementwise
 from tests.guard import FILLS, guarded_alloc  # noqa: F401  (the fixture, by name)
 from tests.lora_bound import assert_lora_elementwise
+from tests.test_gpu_elementwise import _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -367,3 +369,41 @@ def test_two_calls_captured_in_one_linear_graph_replay_with_new_inputs():
         torch.cuda.synchronize()
         for y, r in zip(outs, want):
             assert torch.equal(y, r)
+
+
+# ----------------------------------------------------------------------------- non-finite activations
+_NONFINITE = [("single", (4,), 128, "nf4", 64, (), (3,), "bf16", 3),                    # one 128-k block: every position in it
+              ("bs32", (5, 18), 1024, "nf4", 32, (), (3, 16), "f16", 5),
+              ("ragged", (5, 1, 130), 2176, "fp4", 64, (1,), (16, None, 65), "bf16", 16)]   # 17 blocks: wave 0's second trip holds the tail
+
+
+@pytest.mark.parametrize("Ns, K, qt, bs, bias, Rs, dt, M", [p[1:] for p in _NONFINITE], ids=[p[0] for p in _NONFINITE])
+def test_nonfinite_activations_stay_in_their_rows(guarded_alloc, Ns, K, qt, bs, bias, Rs, dt, M):
+    """The planting passes of tests/nonfinite.py on k_skinny4_group, and on k_lora_down_rows + k_skinny4_group_lora: per pass a NaN row, Inf
+    rows and an untouched row.  Without an adapter a member keeps matmul_4bit's bits on the same planted input; with one, every element is
+    in the class (NaN, +Inf, -Inf, finite) of an explicit float64 IEEE evaluation of x . Wd^T + b + s (B . (A . x)), and a row without a
+    plant keeps, bit for bit, the value it has when no row is planted."""
+    T = DT[dt]
+    weights, biases, decoded, adapters = _group(Ns, K, dt, qt, False, bs, bias, Rs)
+    X0 = _x(K, dt, M)
+    base = F.matmul_4bit_grouped(X0, weights, biases), F.matmul_4bit_lora_grouped(X0, weights, adapters, biases)
+    for one in nonfinite.passes(M, K):
+        X = nonfinite.planted(X0, one)
+        free = nonfinite.untouched_rows(M, one)
+        assert free
+        guarded_alloc.begin(FILLS[0], where=f"M={M}, X{one}")
+        refs = _by_member(X, weights, biases)
+        _reset()
+        got = F.matmul_4bit_grouped(X, weights, biases), F.matmul_4bit_lora_grouped(X, weights, adapters, biases)
+        torch.cuda.synchronize()
+        guarded_alloc.check()
+        assert bn.launch_log == [(len(Ns), M, K, T)] + [(n, total, M, K, T) for n, total in lc.chunks(Rs)], bn.launch_log
+        for i, (y, r) in enumerate(zip(got[0], refs)):
+            assert _same_bits(y, r), f"skinny_group member {i} of {Ns} differs from matmul_4bit with X{one}"
+        for i, (y, r, wd, b, ad) in enumerate(zip(got[1], refs, decoded, biases, adapters)):
+            if ad is None:
+                assert _same_bits(y, r), f"skinny_group_lora member {i} of {Ns} (no adapter) differs from matmul_4bit with X{one}"
+            nonfinite.assert_classes(y, nonfinite.adapter_classes(X, wd, b, ad), f"skinny_group_lora member {i} of {Ns}, X{one}")
+        for ys, bs_ in zip(got, base):
+            for i, (y, y0) in enumerate(zip(ys, bs_)):
+                assert torch.equal(y[free], y0[free]), f"member {i} of {Ns}: a row without a plant changed with X{one}"

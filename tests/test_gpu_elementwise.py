@@ -112,8 +112,8 @@ def _bias(c, N, dt, seed):
     return synthetic.normal_device((N,), dt, seed=seed) if c.get("bias") else None
 
 
-def _weight_4bit(c, N, K, dt, seed):
-    """(packed, QuantState) on the GPU and the oracle's decoded weight [N, K] (a NaN absmax in one block for bad "w")."""
+def _quant_4bit(c, N, K, dt, seed):
+    """The oracle's quantisation of the case's weight on the CPU: (packed, absmax, state2 or None)."""
     qt, bs, cs = c.get("qt", "nf4"), c.get("bs", 64), c.get("cs", False)
     W = synthetic.normal((N, K), dt, seed=seed)
     op, oa, ost2 = oracle.quantize_4bit(W, bs, qt, cs and "bs2" not in c)
@@ -124,6 +124,12 @@ def _weight_4bit(c, N, K, dt, seed):
         assert not cs
         oa = oa.clone()
         oa[oa.numel() // 3] = float("nan")
+    return op, oa, ost2
+
+
+def _state_4bit(c, N, K, dt, op, oa, ost2):
+    """(packed, QuantState) on the GPU of a quantisation and the oracle's decoded weight [N, K]."""
+    qt, bs, cs = c.get("qt", "nf4"), c.get("bs", 64), c.get("cs", False)
     Wd = oracle.dequantize_4bit(op, oa, (N, K), bs, qt, dt, ost2)
     st2 = None
     if cs:
@@ -147,8 +153,13 @@ def _weight_4bit(c, N, K, dt, seed):
     return packed, st, Wd
 
 
-def _weight_8bit(c, N, K, dt, seed, fp8):
-    """(q, scales) on the GPU and the oracle's decoded weight (a NaN row scale / FP8 byte 0x7F for bad "w")."""
+def _weight_4bit(c, N, K, dt, seed):
+    """(packed, QuantState) on the GPU and the oracle's decoded weight [N, K] (a NaN absmax in one block for bad "w")."""
+    return _state_4bit(c, N, K, dt, *_quant_4bit(c, N, K, dt, seed))
+
+
+def _quant_8bit(c, N, K, dt, seed, fp8):
+    """The oracle's row-wise int8 / FP8 quantisation of the case's weight on the CPU: (q, scales)."""
     W = synthetic.normal((N, K), dt, seed=seed, std=0.05)
     q, s = (oracle.quantize_fp8_e4m3 if fp8 else oracle.quantize_rowwise)(W)
     if "w" in c.get("bad", ""):
@@ -158,6 +169,11 @@ def _weight_8bit(c, N, K, dt, seed, fp8):
         else:
             s = s.clone()
             s[N // 2] = float("nan")
+    return q, s
+
+
+def _state_8bit(c, dt, fp8, q, s):
+    """(q, scales) on the GPU of a quantisation and the oracle's decoded weight."""
     Wd = (oracle.dequantize_fp8_e4m3 if fp8 else oracle.dequantize_rowwise)(q, s, dt)
     qd, sd = q.to(DEV), s.to(DEV)
     mine = (F.dequantize_fp8_e4m3 if fp8 else F.dequantize_rowwise)(qd, sd, dt)
@@ -168,6 +184,39 @@ def _weight_8bit(c, N, K, dt, seed, fp8):
     return qd, sd, Wd
 
 
+def _weight_8bit(c, N, K, dt, seed, fp8):
+    """(q, scales) on the GPU and the oracle's decoded weight (a NaN row scale / FP8 byte 0x7F for bad "w")."""
+    return _state_8bit(c, dt, fp8, *_quant_8bit(c, N, K, dt, seed, fp8))
+
+
+def _quantized(c, kind, N, K, dt, seed):
+    """The CPU quantisation behind a quantised linear of `kind` ("4bit", "int8", "fp8"): what _forward takes."""
+    return _quant_4bit(c, N, K, dt, seed) if kind == "4bit" else _quant_8bit(c, N, K, dt, seed, kind == "fp8")
+
+
+def _forward(c, kind, N, K, dt, quant):
+    """(Wd, fwd): the oracle's decode of a quantisation and fwd(X, bias, out_dtype) -> y through the public API."""
+    if kind == "4bit":
+        packed, st, Wd = _state_4bit(c, N, K, dt, *quant)
+        return Wd, lambda X, b=None, out=None: F.matmul_4bit(X, packed, st, b, out)
+    q, s, Wd = _state_8bit(c, dt, kind == "fp8", *quant)
+    if kind == "int8":
+        return Wd, lambda X, b=None, out=None: F.linear_int8(X, q, s, b)
+    return Wd, lambda X, b=None, out=None: F.matmul_fp8_e4m3(X, q, s, b, dt)
+
+
+KIND = {"matmul_4bit": "4bit", "linear_int8": "int8", "matmul_fp8": "fp8"}
+
+
+def _launch(c, call):
+    """call() right after the sentinel launch: (its result, the kernel name), the name and the variant checked against the case."""
+    _sentinel(c["kernel"])
+    y = call()
+    kern = _native.last_kernel()
+    _check_name(kern, c)
+    return y, kern
+
+
 def _run_linear(c, monkeypatch):
     op, N, K, dt = c["op"], c["N"], c["K"], DT[c["dt"]]
     if c.get("fused"):
@@ -175,45 +224,46 @@ def _run_linear(c, monkeypatch):
     X = _activation(c, K, dt, seed=11)
     b = _bias(c, N, dt, seed=12)
     out = DT.get(c.get("out"))
-    if op == "matmul_4bit":
-        packed, st, Wd = _weight_4bit(c, N, K, dt, seed=13)
-        _sentinel(c["kernel"])
-        y = F.matmul_4bit(X, packed, st, b, out)
-    elif op in ("linear_int8", "matmul_fp8"):
-        q, s, Wd = _weight_8bit(c, N, K, dt, seed=13, fp8=op == "matmul_fp8")
-        _sentinel(c["kernel"])
-        y = F.linear_int8(X, q, s, b) if op == "linear_int8" else F.matmul_fp8_e4m3(X, q, s, b, dt)
+    if op in KIND:
+        Wd, fwd = _forward(c, KIND[op], N, K, dt, _quantized(c, KIND[op], N, K, dt, seed=13))
     else:
         Wd = synthetic.normal_device((N, K), dt, seed=13, std=0.05)
-        _sentinel(c["kernel"])
-        y = F.linear_dense(X, Wd, b)
-    kern = _native.last_kernel()
-    _check_name(kern, c)
+        fwd = lambda X, b=None, out=None: F.linear_dense(X, Wd, b)          # noqa: E731
+    y, kern = _launch(c, lambda: fwd(X, b, out))
     return kern, assert_linear_elementwise(y, X, Wd, b, dt, out or dt, kern)
 
 
-def _run_gemm_dense(c):
+def _gemm_dense_operands(c):
+    """(X, Wfull, bias, call) of a mbnb_gemm_dense case: call() poisons the output and the partials and launches on X as it is."""
     M, N, K, ldw, dt = c["M"], c["N"], c["K"], c["ldw"], DT[c["dt"]]
     odt = DT[c.get("out", c["dt"])]
     lib = _native.lib()
     X = _activation(c, K, dt, seed=21)
     Wfull = synthetic.normal_device((N, ldw), dt, seed=22, std=0.05)
     b = _bias(c, N, dt, seed=23)
-    out = _poison(torch.empty(M, N, dtype=odt, device=DEV))
     slices = c["slices"]
-    ws = _poison(torch.empty(slices * M * N * 4, dtype=torch.uint8, device=DEV)) if slices > 1 else None
     code = _native.DTYPE_CODE[dt]
-    _sentinel(c["kernel"])
-    rc = lib.mbnb_gemm_dense(X.data_ptr(), Wfull.data_ptr(), code, None if b is None else b.data_ptr(), _native.DTYPE_CODE[odt],
-                             out.data_ptr(), M, N, K, ldw, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
-                             slices | (c["tile"] << 8), _native.stream_ptr(DEV))
-    assert rc == 0, lib.mbnb_last_error()
-    kern = _native.last_kernel()
-    _check_name(kern, c)
-    return kern, assert_linear_elementwise(out, X, Wfull[:, :K], b, dt, odt, kern)
+
+    def call():
+        out = _poison(torch.empty(M, N, dtype=odt, device=DEV))
+        ws = _poison(torch.empty(slices * M * N * 4, dtype=torch.uint8, device=DEV)) if slices > 1 else None
+        rc = lib.mbnb_gemm_dense(X.data_ptr(), Wfull.data_ptr(), code, None if b is None else b.data_ptr(), _native.DTYPE_CODE[odt],
+                                 out.data_ptr(), M, N, K, ldw, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
+                                 slices | (c["tile"] << 8), _native.stream_ptr(DEV))
+        assert rc == 0, lib.mbnb_last_error()
+        return out
+    return X, Wfull, b, call
 
 
-def _run_matmul_int8(c):
+def _run_gemm_dense(c):
+    K, dt = c["K"], DT[c["dt"]]
+    X, Wfull, b, call = _gemm_dense_operands(c)
+    out, kern = _launch(c, call)
+    return kern, assert_linear_elementwise(out, X, Wfull[:, :K], b, dt, DT[c.get("out", c["dt"])], kern)
+
+
+def _run_matmul_int8(c, plant=None):
+    """plant(sa, sb), if given, changes the row and column scales in place before the launch."""
     M, N, K = c["M"], c["N"], c["K"]
     odt = DT[c["out"]]
     A = synthetic.int8_tensor((M, K), seed=31).to(DEV)
@@ -222,6 +272,8 @@ def _run_matmul_int8(c):
     sb = (synthetic.normal((N,), torch.float32, seed=34).abs() + 0.5).to(DEV)
     if "w" in c.get("bad", ""):
         sb[N // 2] = float("nan")
+    if plant is not None:
+        plant(sa, sb)
     if c.get("view") == "a+1":
         A = _offset(A, 1)
     elif c.get("view") == "b+1":
@@ -233,17 +285,9 @@ def _run_matmul_int8(c):
     return kern, assert_int8_elementwise(y, int8_reference(A, B, sa, sb), odt, kern)
 
 
-def _run_grad(c):
-    """dX = cast(round_w(dY.to(w_dtype) . dequant(W)), x.dtype): the contraction runs over N."""
-    M, N, K, dt, fmt = c["M"], c["N"], c["K"], DT[c["dt"]], c["fmt"]
-    if fmt == "4bit":
-        packed, st, Wd = _weight_4bit(c, N, K, dt, seed=41)
-        fwd = lambda x: F.matmul_4bit(x, packed, st)            # noqa: E731
-    else:
-        q, s, Wd = _weight_8bit(c, N, K, dt, seed=41, fp8=fmt == "fp8")
-        fwd = (lambda x: F.linear_int8(x, q, s)) if fmt == "int8" else (lambda x: F.matmul_fp8_e4m3(x, q, s, None, dt))  # noqa: E731
-    x = synthetic.normal_device((M, K), dt, seed=42).requires_grad_(True)
-    dY = _activation(dict(c, M=M), N, dt, seed=43)
+def _backward(c, fwd, x, dY):
+    """(x.grad, the kernel name) of y = fwd(x) under y.backward(dY), the name taken right after the op's backward."""
+    x = x.detach().requires_grad_(True)
     seen = []
     y = fwd(x)
     # both hooks run on autograd's device thread, whose last-kernel record is its own: the sentinel just before the backward
@@ -254,7 +298,17 @@ def _run_grad(c):
     assert len(seen) == 2, seen
     kern = seen[1]
     _check_name(kern, c)
-    return kern, assert_linear_elementwise(x.grad, dY, Wd.t().contiguous().to(DEV), None, dt, dt, kern)
+    return x.grad, kern
+
+
+def _run_grad(c):
+    """dX = cast(round_w(dY.to(w_dtype) . dequant(W)), x.dtype): the contraction runs over N."""
+    M, N, K, dt, fmt = c["M"], c["N"], c["K"], DT[c["dt"]], c["fmt"]
+    Wd, fwd = _forward(c, fmt, N, K, dt, _quantized(c, fmt, N, K, dt, seed=41))
+    x = synthetic.normal_device((M, K), dt, seed=42)
+    dY = _activation(dict(c, M=M), N, dt, seed=43)
+    dx, kern = _backward(c, fwd, x, dY)
+    return kern, assert_linear_elementwise(dx, dY, Wd.t().contiguous().to(DEV), None, dt, dt, kern)
 
 
 def _run_grad_t(c):

@@ -16,8 +16,10 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _group_native as gn
 from mps_bitsandbytes_amd import _native, synthetic
 from mps_bitsandbytes_amd import functional as F
+from tests import nonfinite
 from tests.elementwise import assert_linear_elementwise
 from tests.guard import FILLS, guarded_alloc  # noqa: F401  (the fixture, by name)
+from tests.test_gpu_elementwise import _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -273,3 +275,28 @@ def test_two_grouped_calls_captured_as_one_chain_replay_with_new_inputs():
         torch.cuda.synchronize()
         for y, r in zip(outs, want):
             assert torch.equal(y, r)
+
+
+# ----------------------------------------------------------------------------- non-finite activations
+@pytest.mark.parametrize("Ns, K, nested, bias, dt", [((5, 1, 130), 1088, False, (1,), "bf16"),      # a partial (and the only) 2048-chunk
+                                                     ((7, 64), 2304, True, (0,), "f16")],           # ... the second one partial, nested absmax
+                         ids=["K1088", "K2304-nested"])
+def test_nonfinite_activations_keep_matmul_4bits_bits(guarded_alloc, Ns, K, nested, bias, dt):
+    """An Inf of either sign at every special place of the row (tests/nonfinite.py), one launch each: every member keeps matmul_4bit's
+    bits on the same planted input (NaN in the same places, every other element bit-equal), and NaN / +-Inf sit exactly where the
+    operands put them -- an Inf past which the row's last chunk reads zeros must not become Inf * 0."""
+    T = DT[dt]
+    weights, biases, decoded = _group(Ns, K, dt, "nf4", nested, bias)
+    for one in nonfinite.passes(1, K):
+        X = nonfinite.planted(_x(K, dt), one)
+        guarded_alloc.begin(FILLS[0], where=f"matmul_4bit_grouped, X{one}")
+        refs = [F.matmul_4bit(X, p, st, b) for (p, st), b in zip(weights, biases)]
+        assert _native.last_variant().startswith("gemv_lean"), _native.last_variant()
+        gn.reset_launch_log()
+        ys = F.matmul_4bit_grouped(X, weights, biases)
+        torch.cuda.synchronize()
+        guarded_alloc.check()
+        assert gn.launch_log == [(len(Ns), K, T)], gn.launch_log
+        for i, (y, r, wd, b) in enumerate(zip(ys, refs, decoded, biases)):
+            assert _same_bits(y, r), f"member {i} of {Ns} differs from matmul_4bit with X{one}"
+            assert_linear_elementwise(y, X, wd, b, T, T, f"gemv_group, X{one}")

@@ -21,8 +21,10 @@ from mps_bitsandbytes_amd import _group_native as gn
 from mps_bitsandbytes_amd import _lora_native as ln
 from mps_bitsandbytes_amd import functional as F
 from tests import lora_cases as lc
+from tests import nonfinite
 from tests.guard import FILLS, guarded_alloc  # noqa: F401  (the fixture, by name)
 from tests.lora_bound import assert_lora_elementwise
+from tests.test_gpu_elementwise import _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -295,3 +297,28 @@ def test_two_fused_calls_captured_in_one_graph_replay_with_new_inputs():
         torch.cuda.synchronize()
         for y, r in zip(outs, want):
             assert torch.equal(y, r)
+
+
+# ----------------------------------------------------------------------------- non-finite activations
+@pytest.mark.parametrize("Ns, K, bias, Rs, dt", [((4,), 1088, (), (3,), "bf16"),                        # a partial (and the only) 2048-chunk
+                                                 ((5, 1, 130), 2112, (1,), (16, None, 65), "f16")],     # the second chunk partial; two slices of B
+                         ids=["K1088", "K2112"])
+def test_nonfinite_activations_land_where_ieee_arithmetic_puts_them(guarded_alloc, Ns, K, bias, Rs, dt):
+    """An Inf of either sign at every special place of the row (tests/nonfinite.py), one call each (k_lora_down + k_gemv4_group_lora): a
+    member without an adapter keeps matmul_4bit's bits on the same planted input; a member with one has every element in the class
+    (NaN, +Inf, -Inf, finite) of an explicit float64 IEEE evaluation of x . Wd^T + b + s (B . (A . x))."""
+    T = DT[dt]
+    weights, adapters, biases, decoded = _group(Ns, K, dt, Rs, bias=bias)
+    for one in nonfinite.passes(1, K):
+        X = nonfinite.planted(_x(K, dt), one)
+        guarded_alloc.begin(FILLS[0], where=f"matmul_4bit_lora_grouped, X{one}")
+        plain = {i: F.matmul_4bit(X, weights[i][0], weights[i][1], biases[i]) for i, R in enumerate(Rs) if R is None}
+        ln.reset_launch_log()
+        ys = F.matmul_4bit_lora_grouped(X, weights, adapters, biases)
+        torch.cuda.synchronize()
+        guarded_alloc.check()
+        assert ln.launch_log == [(n, total, K, T) for n, total in lc.chunks(Rs)], ln.launch_log
+        for i, (y, wd, b, ad) in enumerate(zip(ys, decoded, biases, adapters)):
+            if ad is None:
+                assert _same_bits(y, plain[i]), f"member {i} of {Ns} (no adapter) differs from matmul_4bit with X{one}"
+            nonfinite.assert_classes(y, nonfinite.adapter_classes(X, wd, b, ad), f"gemv_lora member {i} of {Ns}, X{one}")

@@ -22,8 +22,10 @@ from mps_bitsandbytes_amd import _mlora_native as mn
 from mps_bitsandbytes_amd import functional as F
 from tests import lora_cases as lc
 from tests import mlora_cases as mc
+from tests import nonfinite
 from tests.elementwise import assert_bound_elementwise
 from tests.guard import FILLS, guarded_alloc  # noqa: F401  (the fixture, by name)
+from tests.test_gpu_elementwise import _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -351,3 +353,49 @@ def test_two_calls_in_one_linear_graph_replay_with_new_ids_and_a_new_slot():
             for y, r in zip(got, want):
                 assert torch.equal(y, r), f"replay {step} differs from an eager call"
         assert not torch.equal(got[2][3], layers[2].base(A)[3])      # the reloaded slot 1 is in use in row 3
+
+
+# ----------------------------------------------------------------------------- non-finite activations
+_NONFINITE = [("single", (4,), 128, (), (3,), "bf16"),                     # one 128-k block: every position in it
+              ("ragged", (5, 1, 130), 2176, (1,), (3, None, 16), "f16")]    # 17 blocks: wave 0's second trip holds the tail
+
+
+@pytest.mark.parametrize("Ns, K, bias, Rs, dt", [p[1:] for p in _NONFINITE], ids=[p[0] for p in _NONFINITE])
+def test_nonfinite_activations_stay_in_their_rows(guarded_alloc, Ns, K, bias, Rs, dt):
+    """The planting passes of tests/nonfinite.py on k_lora_down_sel + k_skinny4_mlora, five rows with the slots 0, -1, 1, S, 2: over the passes
+    a NaN and an Inf land in rows with an adapter and in rows whose id is outside the bank.  A row without an adapter (and a member without
+    a bank) keeps matmul_4bit's bits on the same planted input; a row with one has every element in the class (NaN, +Inf, -Inf, finite) of
+    an explicit float64 IEEE evaluation of x . Wd^T + b + s (B . (A . x)) with its slot's adapter; a row without a plant keeps, bit for
+    bit, the value it has when no row is planted."""
+    T, S, M = DT[dt], 3, 5
+    ids = [0, -1, 1, S, 2]
+    have = [0 <= i < S for i in ids]
+    weights, biases, decoded, banks = _group(Ns, K, dt, bias=bias, Rs=Rs, S=S)
+    X0 = _x(K, dt, M)
+    base = F.matmul_4bit_multilora_grouped(X0, weights, banks, _ids(ids), biases)
+    planted_with, planted_without = set(), set()
+    for one in nonfinite.passes(M, K):
+        X = nonfinite.planted(X0, one)
+        free = nonfinite.untouched_rows(M, one)
+        assert free
+        for r, _, _ in one:
+            (planted_with if have[r] else planted_without).add(r)
+        guarded_alloc.begin(FILLS[0], where=f"matmul_4bit_multilora_grouped, X{one}")
+        plain = [F.matmul_4bit(X, p, st, b) for (p, st), b in zip(weights, biases)]
+        dev_ids = guarded_alloc.place("ids", _ids(ids))
+        mn.reset_launch_log()
+        ys = F.matmul_4bit_multilora_grouped(X, weights, banks, dev_ids, biases)
+        torch.cuda.synchronize()
+        guarded_alloc.check()
+        assert mn.launch_log == [(n, tot, M, K, T) for n, tot in mc.chunks(Rs)], mn.launch_log
+        for i, (y, y0, r, wd, b, bank) in enumerate(zip(ys, base, plain, decoded, biases, banks)):
+            want = nonfinite.adapter_classes(X, wd, b)
+            for m in range(M):
+                if bank is None or not have[m]:
+                    assert _same_bits(y[m], r[m]), f"member {i} of {Ns}, row {m} (slot {ids[m]}) differs from matmul_4bit with X{one}"
+                else:
+                    s = ids[m]
+                    want[m] = nonfinite.adapter_classes(X[m:m + 1], wd, b, (bank[0][s], bank[1][s], float(bank[2][s])))[0]
+            nonfinite.assert_classes(y, want, f"skinny_mlora member {i} of {Ns}, X{one}")
+            assert torch.equal(y[free], y0[free]), f"member {i} of {Ns}: a row without a plant changed with X{one}"
+    assert planted_with and planted_without
