@@ -79,17 +79,8 @@ def gemm4(x: int, M: int, K: int, quant_type: str, dtype: torch.dtype, blocksize
     """out_g[M, N_g] = x[M, K] . dequant(W_g)^T + bias_g for `members` (any number of Member field tuples; plain values, `x` an
     address): one mbnb_batch_gemm4 call, and so one kernel launch, per MAX_MEMBERS of them.  Returns one flag per call: True =
     launched, False = the library answered NOT_APPLICABLE for that chunk and wrote nothing (its reason: last_error())."""
-    handle = lib()
-    done = []
-    for c0 in range(0, len(members), MAX_MEMBERS):
-        part = np.array(members[c0:c0 + MAX_MEMBERS], dtype=MEMBER_DTYPE)
-        status = handle.mbnb_batch_gemm4(x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize, part.ctypes.data_as(POINTER(Member)),
-                                         len(part), 0, stream)
-        if status != NOT_APPLICABLE:
-            check(status, "gemm4")
-            launch_log.append((len(part), M, K, dtype))
-        done.append(status != NOT_APPLICABLE)
-    return done
+    return _loader.call_chunks(globals(), "mbnb_batch_gemm4", "gemm4", (x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize),
+                               [(members, MEMBER_DTYPE, Member)], (), stream, (M, K, dtype))
 
 
 def gemm4_lora(x: int, M: int, K: int, quant_type: str, dtype: torch.dtype, blocksize: int, members: Sequence[tuple],
@@ -98,15 +89,5 @@ def gemm4_lora(x: int, M: int, K: int, quant_type: str, dtype: torch.dtype, bloc
     one): one mbnb_batch_gemm4_lora call, and so two kernel launches, per MAX_MEMBERS of them.  One flag per call, as gemm4."""
     if len(members) != len(adapters):
         raise ValueError(f"{len(members)} members but {len(adapters)} adapters")
-    handle = lib()
-    done = []
-    for c0 in range(0, len(members), MAX_MEMBERS):
-        part = np.array(members[c0:c0 + MAX_MEMBERS], dtype=MEMBER_DTYPE)
-        rank = np.array(adapters[c0:c0 + MAX_MEMBERS], dtype=ADAPTER_DTYPE)
-        status = handle.mbnb_batch_gemm4_lora(x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize, part.ctypes.data_as(POINTER(Member)),
-                                              rank.ctypes.data_as(POINTER(Adapter)), len(part), 0, stream)
-        if status != NOT_APPLICABLE:
-            check(status, "gemm4_lora")
-            launch_log.append((len(part), int(rank["R"].sum()), M, K, dtype))
-        done.append(status != NOT_APPLICABLE)
-    return done
+    return _loader.call_chunks(globals(), "mbnb_batch_gemm4_lora", "gemm4_lora", (x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize),
+                               [(members, MEMBER_DTYPE, Member), (adapters, ADAPTER_DTYPE, Adapter)], (), stream, (M, K, dtype))

@@ -85,14 +85,5 @@ def gemv4(x: int, K: int, quant_type: str, dtype: torch.dtype, blocksize: int, m
     """out_g = x . dequant(W_g)^T + bias_g for `members` (any number of Member field tuples; plain values, `x` an address): one
     mbnb_group_gemv4 call, and so one kernel launch, per MAX_MEMBERS of them.  Returns one flag per call: True = launched,
     False = the library answered NOT_APPLICABLE for that chunk and wrote nothing (its reason: last_error())."""
-    handle = lib()
-    done = []
-    for c0 in range(0, len(members), MAX_MEMBERS):
-        part = np.array(members[c0:c0 + MAX_MEMBERS], dtype=MEMBER_DTYPE)
-        table = part.ctypes.data_as(POINTER(Member))
-        status = handle.mbnb_group_gemv4(x, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize, table, len(part), 0, stream)
-        if status != NOT_APPLICABLE:
-            check(status, "gemv4")
-            launch_log.append((len(part), K, dtype))
-        done.append(status != NOT_APPLICABLE)
-    return done
+    return _loader.call_chunks(globals(), "mbnb_group_gemv4", "gemv4", (x, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize),
+                               [(members, MEMBER_DTYPE, Member)], (), stream, (K, dtype))

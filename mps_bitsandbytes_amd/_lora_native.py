@@ -89,15 +89,5 @@ def gemv4(x: int, K: int, quant_type: str, dtype: torch.dtype, blocksize: int, m
     chunk and wrote nothing (its reason: last_error())."""
     if len(members) != len(adapters):
         raise ValueError(f"{len(members)} members but {len(adapters)} adapters")
-    handle = lib()
-    done = []
-    for c0 in range(0, len(members), MAX_MEMBERS):
-        part = np.array(members[c0:c0 + MAX_MEMBERS], dtype=MEMBER_DTYPE)
-        rank = np.array(adapters[c0:c0 + MAX_MEMBERS], dtype=ADAPTER_DTYPE)
-        status = handle.mbnb_lora_gemv4(x, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize, part.ctypes.data_as(POINTER(Member)),
-                                        rank.ctypes.data_as(POINTER(Adapter)), len(part), 0, stream)
-        if status != NOT_APPLICABLE:
-            check(status, "gemv4")
-            launch_log.append((len(part), int(rank["R"].sum()), K, dtype))
-        done.append(status != NOT_APPLICABLE)
-    return done
+    return _loader.call_chunks(globals(), "mbnb_lora_gemv4", "gemv4", (x, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize),
+                               [(members, MEMBER_DTYPE, Member), (adapters, ADAPTER_DTYPE, Adapter)], (), stream, (K, dtype))

@@ -92,15 +92,5 @@ def gemm4(x: int, M: int, K: int, quant_type: str, dtype: torch.dtype, blocksize
     (its reason: last_error())."""
     if len(members) != len(banks):
         raise ValueError(f"{len(members)} members but {len(banks)} banks")
-    handle = lib()
-    done = []
-    for c0 in range(0, len(members), MAX_MEMBERS):
-        part = np.array(members[c0:c0 + MAX_MEMBERS], dtype=MEMBER_DTYPE)
-        bank = np.array(banks[c0:c0 + MAX_MEMBERS], dtype=BANK_DTYPE)
-        status = handle.mbnb_mlora_gemm4(x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize, part.ctypes.data_as(POINTER(Member)),
-                                         bank.ctypes.data_as(POINTER(Bank)), ids, len(part), 0, stream)
-        if status != NOT_APPLICABLE:
-            check(status, "gemm4")
-            launch_log.append((len(part), int(bank["R"].sum()), M, K, dtype))
-        done.append(status != NOT_APPLICABLE)
-    return done
+    return _loader.call_chunks(globals(), "mbnb_mlora_gemm4", "gemm4", (x, M, K, QUANT_CODE[quant_type], DTYPE_CODE[dtype], blocksize),
+                               [(members, MEMBER_DTYPE, Member), (banks, BANK_DTYPE, Bank)], (ids,), stream, (M, K, dtype))

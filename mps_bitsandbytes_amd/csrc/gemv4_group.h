@@ -3,10 +3,14 @@
 // row) and the host checks of a member table.  The rank-R adapter epilogue sits behind `if constexpr (LORA)`: with LORA = false the
 // body is k_gemv4_group's, instruction for instruction (DESIGN.md 17 holds the comparison).
 //
-// Host part: include host.h first (fail / vfail / aligned / is16), as the one source file of a library does.
+// Host part: include host.h first (fail / vfail / aligned / is16), as the one source file of a library does.  It also serves the 2 to
+// 16 row libraries (skinny4_group.h): the form and KU dispatch and the checks of an adapter table are written here once.
 #pragma once
-#include "../../include/mbnb_group.h"
+#include "../../include/mbnb_lora.h"      // mbnb_group.h, and the adapter table
 #include "gemv4_lean.h"
+
+#include <math.h>
+#include <type_traits>
 
 namespace mbnb {
 
@@ -188,6 +192,28 @@ __device__ __forceinline__ void group_workgroup(const GroupArgs &a, const LoraRo
 // KU of the instantiation that serves ceil(K / 2048) = ku chunks (the lean launcher's choice)
 static int group_ku_form(int ku) { return ku <= 4 ? ku : ku <= 6 ? 6 : 8; }
 
+// f(KU as a compile-time constant) for a KU that group_ku_form gave: the launches of every kernel that has a KU form
+template <typename F> void with_ku(int KU, F &&f) {
+    switch (KU) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+    }
+}
+
+// FN<T, QT, NESTED>(...) for the call's form: {f16, bf16} x {NF4, FP4} x {plain, double-quantised absmax}
+#define MBNB_GROUP_FORMS(DTYPE, QUANT, NESTED, FN, ...)                                                                             \
+    ((DTYPE) == MBNB_GROUP_F16                                                                                                      \
+         ? ((QUANT) == MBNB_GROUP_NF4                                                                                               \
+                ? ((NESTED) ? FN<mbnb::f16_t, MBNB_NF4, true>(__VA_ARGS__) : FN<mbnb::f16_t, MBNB_NF4, false>(__VA_ARGS__))         \
+                : ((NESTED) ? FN<mbnb::f16_t, MBNB_FP4, true>(__VA_ARGS__) : FN<mbnb::f16_t, MBNB_FP4, false>(__VA_ARGS__)))        \
+         : ((QUANT) == MBNB_GROUP_NF4                                                                                               \
+                ? ((NESTED) ? FN<mbnb::bf16_t, MBNB_NF4, true>(__VA_ARGS__) : FN<mbnb::bf16_t, MBNB_NF4, false>(__VA_ARGS__))       \
+                : ((NESTED) ? FN<mbnb::bf16_t, MBNB_FP4, true>(__VA_ARGS__) : FN<mbnb::bf16_t, MBNB_FP4, false>(__VA_ARGS__))))
+
 // ---------------------------------------------------------------- host side: the checks of a member table, for both libraries
 // `who` is the entry point's name in the error texts.  group_argument_errors: 0, or the negative code of an argument error (n == 0 is
 // the caller's no-op and never comes here).  group_conditions: 0 with `a` filled and `nested` set, or `not_applicable` after recording
@@ -245,6 +271,47 @@ static int group_conditions(const char *who, int not_applicable, const void *x, 
     }
     for (int i = n; i <= kGroupMax; ++i) a.first_block[i] = (int32_t)blocks;
     for (int i = n; i < kGroupMax; ++i) a.m[i] = mbnb_group_member{};
+    return 0;
+}
+
+// ---------------------------------------------------------------- host side: the checks of an adapter table, one adapter per member
+// adapter_argument_errors: 0, or the negative code of an argument error.  adapter_conditions: 0 with rows[kGroupMax] filled and, in
+// the down-projection table `d` (a library's own DownArgs), first_row[kGroupMax + 1] and every m[i].a / m[i].t, or `not_applicable`
+// after recording the reason; `plain` names the entry point that serves a table without any adapter.
+static_assert(MBNB_LORA_ERR_ARG == MBNB_GROUP_ERR_ARG && MBNB_LORA_ERR_SHAPE == MBNB_GROUP_ERR_SHAPE, "one set of argument-error codes");
+static int adapter_argument_errors(const char *who, const mbnb_lora_adapter *adapters, int n) {
+    if (!adapters) return fail(MBNB_LORA_ERR_ARG, "%s: NULL adapter table", who);
+    for (int i = 0; i < n; ++i) {
+        const mbnb_lora_adapter &ad = adapters[i];
+        if (ad.R < 0) return fail(MBNB_LORA_ERR_SHAPE, "%s: member %d has R = %d", who, i, ad.R);
+        if (ad.R > 0 && (!ad.a || !ad.b)) return fail(MBNB_LORA_ERR_ARG, "%s: member %d has R = %d with a NULL a or b", who, i, ad.R);
+    }
+    return 0;
+}
+
+template <typename Down>
+int adapter_conditions(const char *who, int not_applicable, const char *plain, const mbnb_lora_adapter *adapters, int n, Down &d, LoraRow *rows) {
+    const int na = not_applicable;
+    int total = 0;
+    for (int i = 0; i < kGroupMax; ++i) {
+        d.first_row[i] = total;
+        d.m[i].a = nullptr;
+        d.m[i].t = nullptr;
+        rows[i] = LoraRow{nullptr, nullptr, 0, 0.0f};
+        if (i >= n || adapters[i].R == 0) continue;
+        const mbnb_lora_adapter &ad = adapters[i];
+        if (ad.R > MBNB_LORA_MAX_R) return fail(na, "%s: member %d has R = %d, 1 <= R <= %d is needed", who, i, ad.R, MBNB_LORA_MAX_R);
+        if (!aligned(ad.a, 16)) return fail(na, "%s: member %d's a is not 16-byte aligned", who, i);
+        if (!aligned(ad.b, 2)) return fail(na, "%s: member %d's b is not 2-byte aligned", who, i);
+        if (!ad.t || !aligned(ad.t, 4)) return fail(na, "%s: member %d's t is NULL or not 4-byte aligned", who, i);
+        if (!isfinite(ad.scaling)) return fail(na, "%s: member %d's scaling is not finite", who, i);
+        d.m[i].a = ad.a;
+        d.m[i].t = ad.t;
+        rows[i] = LoraRow{ad.b, ad.t, ad.R, ad.scaling};
+        total += ad.R;
+    }
+    d.first_row[kGroupMax] = total;
+    if (total == 0) return fail(na, "%s: no member has an adapter (R > 0): the call is %s's", who, plain);
     return 0;
 }
 

@@ -15,9 +15,9 @@ static_assert(MBNB_GROUP_NF4 == MBNB_NF4 && MBNB_GROUP_FP4 == MBNB_FP4, "code ta
 
 namespace {
 
-using mbnb::bf16_t;
-using mbnb::f16_t;
 using mbnb::GroupArgs;
+using mbnb::kLaunchBytes;
+using mbnb::last_launch;
 
 // the member table, the workgroup body and the row body (a marked copy of k_gemv4_lean's) are in gemv4_group.h, shared with
 // k_gemv4_group_lora of libmbnb_lora.so; LORA = false here
@@ -29,37 +29,18 @@ __global__ __launch_bounds__(256) void k_gemv4_group(const GroupArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-char *last_launch() {
-    static thread_local char text[64] = "";
-    return text;
-}
-
 template <typename T, int QT, bool NESTED>
 int launch(const GroupArgs &a, hipStream_t stream) {
     const int ku = (int)((a.K + 2047) / 2048);
+    const int KU = mbnb::group_ku_form(ku);
     const dim3 grid((unsigned)a.first_block[a.n]);
-    int KU;
-#define MBNB_GROUP(KU_)                                                                                               \
-    do {                                                                                                              \
-        hipLaunchKernelGGL((k_gemv4_group<T, QT, NESTED, KU_>), grid, dim3(256), (size_t)KU_ * 4096, stream, a);      \
-        KU = KU_;                                                                                                     \
-    } while (0)
-    if (ku == 1) MBNB_GROUP(1);
-    else if (ku == 2) MBNB_GROUP(2);
-    else if (ku == 3) MBNB_GROUP(3);
-    else if (ku == 4) MBNB_GROUP(4);
-    else if (ku <= 6) MBNB_GROUP(6);
-    else MBNB_GROUP(8);
-#undef MBNB_GROUP
+    mbnb::with_ku(KU, [&](auto ku_) {
+        constexpr int KU_ = decltype(ku_)::value;
+        hipLaunchKernelGGL((k_gemv4_group<T, QT, NESTED, KU_>), grid, dim3(256), (size_t)KU_ * 4096, stream, a);
+    });
     const int rc = mbnb::launch_status("mbnb_group_gemv4");
-    if (rc == 0) snprintf(last_launch(), 64, "gemv_group G%d ku%d/KU%d", a.n, ku, KU);
+    if (rc == 0) snprintf(last_launch(), kLaunchBytes, "gemv_group G%d ku%d/KU%d", a.n, ku, KU);
     return rc;
-}
-
-template <typename T>
-int dispatch_form(int qt, bool nested, const GroupArgs &a, hipStream_t stream) {
-    if (qt == MBNB_GROUP_NF4) return nested ? launch<T, MBNB_NF4, true>(a, stream) : launch<T, MBNB_NF4, false>(a, stream);
-    return nested ? launch<T, MBNB_FP4, true>(a, stream) : launch<T, MBNB_FP4, false>(a, stream);
 }
 
 }  // namespace
@@ -82,7 +63,7 @@ int mbnb_group_gemv4(const void *x, int64_t K, int quant_type, int dtype, int bl
     bool nested;
     if (const int rc = mbnb::group_conditions(who, MBNB_GROUP_NOT_APPLICABLE, x, K, dtype, blocksize, members, n, a, nested)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    return dtype == MBNB_GROUP_F16 ? dispatch_form<f16_t>(quant_type, nested, a, s) : dispatch_form<bf16_t>(quant_type, nested, a, s);
+    return MBNB_GROUP_FORMS(dtype, quant_type, nested, launch, a, s);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// host.h — what the host side of all seven libraries shares: the thread-local error text behind each library's *_last_error(), the
-// launch check, and the small argument predicates.  Host code only; the two element types come from elem_types.h.
+// host.h — what the host side of all nine libraries shares: the thread-local error text behind each library's *_last_error(), the
+// last-launch text behind *_last_launch() of the four grouped decode libraries, the launch check, and the small argument predicates.  Host code only; the two element types come from elem_types.h.
 //
 // Included by the ONE source file of a library that owns its error text: the source of each satellite library, and api.hip for
 // libmbnb_hip.so, whose kernel sources include common.h alone and report through its set_error() / check_launch().  The functions
@@ -20,6 +20,15 @@ constexpr int kErrorBytes = 512;
 
 static char *last_error() {
     static thread_local char text[kErrorBytes] = "";
+    return text;
+}
+
+// the text behind *_last_launch() of the libraries that have one: the form of this thread's last fused launch, written with
+// snprintf(last_launch(), kLaunchBytes, ...) after a launch that succeeded
+constexpr int kLaunchBytes = 128;
+
+static char *last_launch() {
+    static thread_local char text[kLaunchBytes] = "";
     return text;
 }
 

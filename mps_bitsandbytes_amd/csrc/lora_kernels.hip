@@ -11,8 +11,6 @@
 #include "host.h"
 #include "gemv4_group.h"
 
-#include <math.h>
-
 static_assert(MBNB_LORA_ERR_ARG == MBNB_GROUP_ERR_ARG && MBNB_LORA_ERR_SHAPE == MBNB_GROUP_ERR_SHAPE, "the argument checks are shared");
 static_assert(MBNB_LORA_NOT_APPLICABLE == MBNB_GROUP_NOT_APPLICABLE, "one NOT_APPLICABLE");
 static_assert(MBNB_LORA_MAX_R == mbnb::kLoraMaxR, "the row epilogue's slices");
@@ -20,13 +18,11 @@ static_assert(MBNB_GROUP_F16 == mbnb::kF16 && MBNB_GROUP_BF16 == mbnb::kBF16 && 
 
 namespace {
 
-using mbnb::aligned;
-using mbnb::bf16_t;
 using mbnb::Dot2;
 using mbnb::dpp_wave_sum;
-using mbnb::f16_t;
-using mbnb::fail;
 using mbnb::GroupArgs;
+using mbnb::kLaunchBytes;
+using mbnb::last_launch;
 using mbnb::LoraRow;
 using mbnb::u32x4;
 
@@ -98,42 +94,21 @@ __global__ __launch_bounds__(256) void k_gemv4_group_lora(const LoraArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-constexpr int kLaunchBytes = 96;
-char *last_launch() {
-    static thread_local char text[kLaunchBytes] = "";
-    return text;
-}
-
 template <typename T, int QT, bool NESTED>
 int launch(const DownArgs &d, const LoraArgs &a, hipStream_t stream) {
     const int ku = (int)((a.g.K + 2047) / 2048);
     const int KU = mbnb::group_ku_form(ku);
     const dim3 down((unsigned)d.first_row[d.n]), grid((unsigned)a.g.first_block[a.g.n]);
-#define MBNB_LORA(KU_)                                                                                                    \
-    case KU_:                                                                                                             \
-        hipLaunchKernelGGL((k_lora_down<T, KU_>), down, dim3(256), 0, stream, d);                                         \
-        hipLaunchKernelGGL((k_gemv4_group_lora<T, QT, NESTED, KU_>), grid, dim3(256), (size_t)KU_ * 4096, stream, a);     \
-        break
-    switch (KU) {
-        MBNB_LORA(1);
-        MBNB_LORA(2);
-        MBNB_LORA(3);
-        MBNB_LORA(4);
-        MBNB_LORA(6);
-        MBNB_LORA(8);
-    }
-#undef MBNB_LORA
+    mbnb::with_ku(KU, [&](auto ku_) {
+        constexpr int KU_ = decltype(ku_)::value;
+        hipLaunchKernelGGL((k_lora_down<T, KU_>), down, dim3(256), 0, stream, d);
+        hipLaunchKernelGGL((k_gemv4_group_lora<T, QT, NESTED, KU_>), grid, dim3(256), (size_t)KU_ * 4096, stream, a);
+    });
     const int rc = mbnb::launch_status("mbnb_lora_gemv4");
     if (rc == 0)
         snprintf(last_launch(), kLaunchBytes, "lora_down G%d R%d ku%d/KU%d + gemv_lora G%d ku%d/KU%d", d.n, d.first_row[d.n], ku, KU, a.g.n, ku,
                  KU);
     return rc;
-}
-
-template <typename T>
-int dispatch_form(int qt, bool nested, const DownArgs &d, const LoraArgs &a, hipStream_t stream) {
-    if (qt == MBNB_GROUP_NF4) return nested ? launch<T, MBNB_NF4, true>(d, a, stream) : launch<T, MBNB_NF4, false>(d, a, stream);
-    return nested ? launch<T, MBNB_FP4, true>(d, a, stream) : launch<T, MBNB_FP4, false>(d, a, stream);
 }
 
 }  // namespace
@@ -152,13 +127,8 @@ int mbnb_lora_gemv4(const void *x, int64_t K, int quant_type, int dtype, int blo
     static const char who[] = "mbnb_lora_gemv4";
     // ---- argument errors: mbnb_group_gemv4's, then the adapter table's
     if (const int rc = mbnb::group_argument_errors(who, x, K, quant_type, dtype, blocksize, members, n, flags)) return rc;
-    if (!adapters) return fail(MBNB_LORA_ERR_ARG, "%s: NULL adapter table", who);
-    for (int i = 0; i < n; ++i) {
-        const mbnb_lora_adapter &ad = adapters[i];
-        if (ad.R < 0) return fail(MBNB_LORA_ERR_SHAPE, "%s: member %d has R = %d", who, i, ad.R);
-        if (ad.R > 0 && (!ad.a || !ad.b)) return fail(MBNB_LORA_ERR_ARG, "%s: member %d has R = %d with a NULL a or b", who, i, ad.R);
-    }
-    // ---- the conditions of the fused launches: mbnb_group_gemv4's (gemv4_group.h), then the adapters'; this is the one place these live
+    if (const int rc = mbnb::adapter_argument_errors(who, adapters, n)) return rc;
+    // ---- the conditions of the fused launches: mbnb_group_gemv4's, then the adapters' (both in gemv4_group.h: the one place these live)
     LoraArgs a;
     bool nested;
     if (const int rc = mbnb::group_conditions(who, MBNB_LORA_NOT_APPLICABLE, x, K, dtype, blocksize, members, n, a.g, nested)) return rc;
@@ -166,35 +136,9 @@ int mbnb_lora_gemv4(const void *x, int64_t K, int quant_type, int dtype, int blo
     d.x = x;
     d.K = K;
     d.n = n;
-    int rows = 0;
-    for (int i = 0; i < n; ++i) {
-        const mbnb_lora_adapter &ad = adapters[i];
-        d.first_row[i] = rows;
-        if (ad.R == 0) {
-            d.m[i].a = nullptr;
-            d.m[i].t = nullptr;
-            a.rows[i] = LoraRow{nullptr, nullptr, 0, 0.0f};
-            continue;
-        }
-        if (ad.R > MBNB_LORA_MAX_R) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: member %d has R = %d, 1 <= R <= %d is needed", who, i, ad.R, MBNB_LORA_MAX_R);
-        if (!aligned(ad.a, 16)) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: member %d's a is not 16-byte aligned", who, i);
-        if (!aligned(ad.b, 2)) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: member %d's b is not 2-byte aligned", who, i);
-        if (!ad.t || !aligned(ad.t, 4)) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: member %d's t is NULL or not 4-byte aligned", who, i);
-        if (!isfinite(ad.scaling)) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: member %d's scaling is not finite", who, i);
-        d.m[i].a = ad.a;
-        d.m[i].t = ad.t;
-        a.rows[i] = LoraRow{ad.b, ad.t, ad.R, ad.scaling};
-        rows += ad.R;
-    }
-    if (rows == 0) return fail(MBNB_LORA_NOT_APPLICABLE, "%s: no member has an adapter (R > 0): the call is mbnb_group_gemv4's", who);
-    for (int i = n; i <= kMax; ++i) d.first_row[i] = rows;
-    for (int i = n; i < kMax; ++i) {
-        d.m[i].a = nullptr;
-        d.m[i].t = nullptr;
-        a.rows[i] = LoraRow{nullptr, nullptr, 0, 0.0f};
-    }
+    if (const int rc = mbnb::adapter_conditions(who, MBNB_LORA_NOT_APPLICABLE, "mbnb_group_gemv4", adapters, n, d, a.rows)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    return dtype == MBNB_GROUP_F16 ? dispatch_form<f16_t>(quant_type, nested, d, a, s) : dispatch_form<bf16_t>(quant_type, nested, d, a, s);
+    return MBNB_GROUP_FORMS(dtype, quant_type, nested, launch, d, a, s);
 }
 
 }  // extern "C"

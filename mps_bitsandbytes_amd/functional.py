@@ -705,21 +705,45 @@ def matmul_4bit_grouped(
         raise ValueError(f"matmul_4bit_grouped: {len(weights)} weights but {len(biases)} biases")
     if not weights:
         return ()
-    plan = _group_rows(A, weights, biases, compute_dtype, _batch_native.MAX_M)
-    if plan is None:
-        return tuple(matmul_4bit(A, B, state, bias, compute_dtype) for (B, state), bias in zip(weights, biases))
-    K, qt, blocksize, w_dtype, rows, keep = plan
-    M = A.numel() // K
-    x, table, outs = _group_table(A, K, w_dtype, rows, M)
-    with on_device(A.device):
+    def launch(x, M, K, qt, w_dtype, blocksize, table, _, stream):
         if M == 1:
-            launched = _group_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
-        else:
-            launched = _batch_native.gemm4(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, stream_ptr(A.device))
+            return _group_native.gemv4(x, K, qt, w_dtype, blocksize, table, stream)
+        return _batch_native.gemm4(x, M, K, qt, w_dtype, blocksize, table, stream)
+
+    return _grouped_launch(A, weights, biases, compute_dtype, _batch_native.MAX_M, launch,
+                           lambda i: matmul_4bit(A, weights[i][0], weights[i][1], biases[i], compute_dtype))
+
+
+def _grouped_launch(A: Tensor, weights, biases, compute_dtype: Optional[torch.dtype], max_rows: int, launch, fallback,
+                    rank_check=None, rank_of=None, table_row=None):
+    """What the three grouped functions do once their arguments are validated: the plan (_group_rows), the member table and the
+    outputs (_group_table), the f32 workspace t laid out member by member, the launch, and `fallback(i)` for every member of a chunk
+    the library declined -- or for every member, where there is no plan.
+
+    `launch(x, M, K, quant_type, w_dtype, blocksize, table, side_table, stream)` returns one flag per call of the library.  The last
+    three arguments belong to a function with adapters: `rank_check(K, w_dtype, rows, M)` gives one entry per member (None: no
+    adapter) or None where the fused launch cannot take them, `rank_of(entry)` its R, and `table_row(entry, t)` the row of the side
+    table for an entry whose f32 [M, R] block of the workspace starts at address `t`."""
+    plan = _group_rows(A, weights, biases, compute_dtype, max_rows)
+    M = 0 if plan is None else A.numel() // plan[0]
+    ranks = None if plan is None else [] if rank_check is None else rank_check(plan[0], plan[3], plan[4], M)
+    if ranks is None:
+        return tuple(fallback(i) for i in range(len(weights)))
+    K, qt, blocksize, w_dtype, rows, keep = plan
+    x, table, outs = _group_table(A, K, w_dtype, rows, M)
+    side = None
+    if rank_check is not None:
+        t = torch.empty(M * sum(rank_of(r) for r in ranks if r is not None), dtype=torch.float32, device=A.device)
+        side, t0, o = [], t.data_ptr(), 0
+        for r in ranks:
+            side.append(table_row(r, t0 + 4 * o))      # t: the f32 [M, R] block of this member
+            o += 0 if r is None else M * rank_of(r)
+    with on_device(A.device):
+        launched = launch(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, side, stream_ptr(A.device))
     for c, ok in enumerate(launched):
-        if not ok:    # the library declined this chunk before launching anything: its members one by one
+        if not ok:    # the library declined this chunk before launching anything: its members through the fallback
             for i in range(c * _group_native.MAX_MEMBERS, min((c + 1) * _group_native.MAX_MEMBERS, len(rows))):
-                outs[i] = matmul_4bit(A, weights[i][0], weights[i][1], biases[i], compute_dtype)
+                outs[i] = fallback(i)
     return tuple(outs)
 
 
@@ -821,34 +845,16 @@ def matmul_4bit_lora_grouped(
     if all(adapter is None for adapter in adapters):
         return matmul_4bit_grouped(A, weights, biases, compute_dtype)
 
-    def composed(i):
-        return _lora_composed(A, weights[i][0], weights[i][1], biases[i], adapters[i], compute_dtype)
-
-    plan = _group_rows(A, weights, biases, compute_dtype, _batch_native.MAX_M)
-    ranks = None if plan is None else _lora_ranks(A, plan[0], plan[3], plan[4], adapters)
-    if ranks is None:
-        return tuple(composed(i) for i in range(len(weights)))
-    K, qt, blocksize, w_dtype, rows, keep = plan
-    M = A.numel() // K
-    x, table, outs = _group_table(A, K, w_dtype, rows, M)
-    t = torch.empty(M * sum(r[2] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
-    rank_table, t0, o = [], t.data_ptr(), 0
-    for r in ranks:
-        if r is None:
-            rank_table.append(_lora_native.NO_ADAPTER)
-        else:
-            rank_table.append((r[0].data_ptr(), r[1].data_ptr(), t0 + 4 * o, r[2], r[3]))      # t: the f32 [M, R] block of this member
-            o += M * r[2]
-    with on_device(A.device):
+    def launch(x, M, K, qt, w_dtype, blocksize, table, rank_table, stream):
         if M == 1:
-            launched = _lora_native.gemv4(x.data_ptr(), K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
-        else:
-            launched = _batch_native.gemm4_lora(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, rank_table, stream_ptr(A.device))
-    for c, ok in enumerate(launched):
-        if not ok:    # the library declined this chunk before launching anything: its members in the composed form
-            for i in range(c * _lora_native.MAX_MEMBERS, min((c + 1) * _lora_native.MAX_MEMBERS, len(rows))):
-                outs[i] = composed(i)
-    return tuple(outs)
+            return _lora_native.gemv4(x, K, qt, w_dtype, blocksize, table, rank_table, stream)
+        return _batch_native.gemm4_lora(x, M, K, qt, w_dtype, blocksize, table, rank_table, stream)
+
+    return _grouped_launch(A, weights, biases, compute_dtype, _batch_native.MAX_M, launch,
+                           lambda i: _lora_composed(A, weights[i][0], weights[i][1], biases[i], adapters[i], compute_dtype),
+                           lambda K, w_dtype, rows, M: _lora_ranks(A, K, w_dtype, rows, adapters),
+                           lambda r: r[2],
+                           lambda r, t: _lora_native.NO_ADAPTER if r is None else (r[0].data_ptr(), r[1].data_ptr(), t, r[2], r[3]))
 
 
 def _multilora_ranks(A: Tensor, K: int, w_dtype: torch.dtype, rows, banks):
@@ -938,33 +944,22 @@ def matmul_4bit_multilora_grouped(
     if adapter_ids.dtype.is_floating_point or adapter_ids.dtype.is_complex or adapter_ids.dtype == torch.bool:
         raise TypeError(f"matmul_4bit_multilora_grouped: adapter_ids must be an integer tensor, got {adapter_ids.dtype}")
 
-    def composed(i):
-        return _multilora_composed(A, weights[i][0], weights[i][1], biases[i], banks[i], adapter_ids, compute_dtype)
+    ids = adapter_ids
 
-    plan = _group_rows(A, weights, biases, compute_dtype, _mlora_native.MAX_M)
-    M = 0 if plan is None else A.numel() // plan[0]
-    ranks = None if plan is None or M < _mlora_native.MIN_M or adapter_ids.device != A.device else \
-        _multilora_ranks(A, plan[0], plan[3], plan[4], banks)
-    if ranks is None:
-        return tuple(composed(i) for i in range(len(weights)))
-    K, qt, blocksize, w_dtype, rows, keep = plan
-    ids = adapter_ids if adapter_ids.dtype == torch.int32 and adapter_ids.is_contiguous() else adapter_ids.to(torch.int32).contiguous()
-    x, table, outs = _group_table(A, K, w_dtype, rows, M)
-    t = torch.empty(M * sum(r[3] for r in ranks if r is not None), dtype=torch.float32, device=A.device)
-    bank_table, t0, o = [], t.data_ptr(), 0
-    for r in ranks:
-        if r is None:
-            bank_table.append(_mlora_native.NO_BANK)
-        else:
-            bank_table.append((r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(), t0 + 4 * o, r[3], r[4]))      # t: the f32 [M, R] block of this member
-            o += M * r[3]
-    with on_device(A.device):
-        launched = _mlora_native.gemm4(x.data_ptr(), M, K, qt, w_dtype, blocksize, table, bank_table, ids.data_ptr(), stream_ptr(A.device))
-    for c, ok in enumerate(launched):
-        if not ok:    # the library declined this chunk before launching anything: its members in the composed form
-            for i in range(c * _mlora_native.MAX_MEMBERS, min((c + 1) * _mlora_native.MAX_MEMBERS, len(rows))):
-                outs[i] = composed(i)
-    return tuple(outs)
+    def rank_check(K, w_dtype, rows, M):
+        nonlocal ids
+        ranks = None if M < _mlora_native.MIN_M or adapter_ids.device != A.device else _multilora_ranks(A, K, w_dtype, rows, banks)
+        if ranks is not None and not (ids.dtype == torch.int32 and ids.is_contiguous()):
+            ids = ids.to(torch.int32).contiguous()      # once per call, before the outputs are allocated
+        return ranks
+
+    def launch(x, M, K, qt, w_dtype, blocksize, table, bank_table, stream):
+        return _mlora_native.gemm4(x, M, K, qt, w_dtype, blocksize, table, bank_table, ids.data_ptr(), stream)
+
+    return _grouped_launch(A, weights, biases, compute_dtype, _mlora_native.MAX_M, launch,
+                           lambda i: _multilora_composed(A, weights[i][0], weights[i][1], biases[i], banks[i], adapter_ids, compute_dtype),
+                           rank_check, lambda r: r[3],
+                           lambda r, t: _mlora_native.NO_BANK if r is None else (r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(), t, r[3], r[4]))
 
 
 def matmul_int8(A: Tensor, B: Tensor, A_scales: Tensor, B_scales: Tensor,

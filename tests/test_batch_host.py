@@ -66,11 +66,14 @@ def test_the_other_seven_libraries_export_none_of_it_and_it_links_none_of_them()
 
 def test_source_reports_through_its_own_export():
     """The kernel-name closure tests scan every csrc file for these two calls; this library reports through mbnb_batch_last_launch()."""
-    for path in (SOURCE, HEADER, bn.__file__):
+    shared = os.path.join(os.path.dirname(SOURCE), "skinny4_group.h")
+    for path in (SOURCE, shared, HEADER, bn.__file__):
         src = open(path).read()
         assert "set_kernel_name" not in src and "set_kernel_variant" not in src, path
     src = open(SOURCE).read()
-    assert "mbnb_batch_last_launch" in src and "atomic" not in src.replace("no atomics", "")
+    assert "mbnb_batch_last_launch" in src
+    for path in (SOURCE, shared):
+        assert "atomic" not in open(path).read().replace("no atomics", ""), path
     makefile = open(os.path.join(os.path.dirname(SOURCE), "Makefile")).read()
     assert re.search(r"^LIBS\s*\+=\s*batch$", makefile, flags=re.M) and re.search(r"^batch_SRCS\s*:=\s*batch_kernels\.hip$", makefile, flags=re.M)
     assert "batch" not in re.search(r"^NEEDS_HIP\s*:=(.*)$", makefile, flags=re.M).group(1)
