@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _mx_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -1833,3 +1833,125 @@ def dequant_absmax(absmax_quant: Tensor, absmax_scales, blocksize: int = 256) ->
         check(_native.lib().mbnb_dequant_absmax(ptr(q), kind, rows, num_blocks, ptr(scales), dq_blocks, int(blocksize),
                                                 ptr(out), stream_ptr(q.device)), "dequant_absmax")
     return out
+
+
+# ============================================================================= OCP MX (MXFP4 weights, MXFP4 / MXFP8 activations)
+# No counterpart in the reference: its FP4 table is not E2M1 and its scales are f32.  The format is DESIGN.md §25 and
+# include/mbnb_mx.h: codes plus one E8M0 scale byte per 32 consecutive k, both row-major, so the tensors are the ones other MX
+# tools read and write.  The linear runs gfx950's block-scaled MFMA over them as they lie in memory (libmbnb_mx.so).
+def _mx_elem(elem: str, what: str) -> int:
+    try:
+        return _mx_native.ELEM_CODE[elem]
+    except (KeyError, TypeError):
+        raise ValueError(f"{what}: unknown MX element format {elem!r} (supported: 'fp4', 'fp8')") from None
+
+
+def _mx_width(K: int, what: str) -> None:
+    if K <= 0 or K % _mx_native.BLOCK:
+        raise ValueError(f"{what}: the last dimension ({K}) must be a positive multiple of the MX block, {_mx_native.BLOCK}")
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def quantize_mx(tensor: Tensor, elem: str = "fp4") -> Tuple[Tensor, Tensor]:
+    """
+    Quantise a 2-D tensor [rows, K] (K % 32 == 0) to OCP MX: returns (codes, scales) with `scales` uint8 [rows, K / 32]
+    (E8M0, 0xFF = NaN block) and `codes` uint8 [rows, K / 2] for elem "fp4" (E2M1, even k in the low nibble) or
+    [rows, K] for "fp8" (E4M3).  The rule is DESIGN.md §25.
+    """
+    code = _mx_elem(elem, "quantize_mx")
+    _check_device(tensor, "quantize_mx")
+    if tensor.dim() != 2:
+        raise ValueError("quantize_mx: input must be 2D")
+    rows, K = tensor.shape
+    _mx_width(K, "quantize_mx")
+    x = _aligned16(tensor if tensor.dtype in _native.DTYPE_CODE else tensor.float())
+    codes = torch.empty(rows, K // 2 if code == _mx_native.FP4 else K, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(rows, K // _mx_native.BLOCK, dtype=torch.uint8, device=x.device)
+    with on_device(x.device):
+        _mx_native.check(_mx_native.lib().mbnb_mx_quantize(ptr(x), rows, K, dtype_code(x.dtype, "quantize_mx"), code, ptr(codes),
+                                                           ptr(scales), stream_ptr(x.device)), "quantize_mx")
+    return codes, scales
+
+
+def dequantize_mx(codes: Tensor, scales: Tensor, elem: str = "fp4", dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """value(code) * 2^(scale byte - 127), formed exactly and rounded once to `dtype`; a 0xFF scale byte gives a NaN block."""
+    code = _mx_elem(elem, "dequantize_mx")
+    _check_device(codes, "dequantize_mx")
+    if codes.dim() != 2 or scales.dim() != 2 or codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError("dequantize_mx: codes and scales must be 2D uint8 tensors")
+    rows = codes.shape[0]
+    K = codes.shape[1] * 2 if code == _mx_native.FP4 else codes.shape[1]
+    _mx_width(K, "dequantize_mx")
+    if tuple(scales.shape) != (rows, K // _mx_native.BLOCK):
+        raise ValueError(f"dequantize_mx: scales {tuple(scales.shape)} do not match codes {tuple(codes.shape)}: expected {(rows, K // _mx_native.BLOCK)}")
+    q = _aligned16(codes)
+    s = scales.to(q.device).contiguous()
+    out = torch.empty(rows, K, dtype=dtype, device=q.device)
+    with on_device(q.device):
+        _mx_native.check(_mx_native.lib().mbnb_mx_dequantize(ptr(q), ptr(s), rows, K, code, dtype_code(dtype, "dequantize_mx"), ptr(out),
+                                                             stream_ptr(q.device)), "dequantize_mx")
+    return out
+
+
+def quantize_mxfp4(tensor: Tensor) -> Tuple[Tensor, Tensor]:
+    """``quantize_mx(tensor, "fp4")``"""
+    return quantize_mx(tensor, "fp4")
+
+
+def dequantize_mxfp4(codes: Tensor, scales: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """``dequantize_mx(codes, scales, "fp4", dtype)``"""
+    return dequantize_mx(codes, scales, "fp4", dtype)
+
+
+def matmul_mxfp4(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None, act_format: str = "fp8",
+                 dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    ``Q(input[..., K]) @ W^T + bias`` with W the MXFP4 weight (`weight` uint8 [N, K / 2], `weight_scales` uint8 [N, K / 32]) and Q
+    the MX quantiser of the activation rows to `act_format` ("fp8": E4M3, "fp4": E2M1).  Two launches: the quantiser into a
+    workspace, then the block-scaled MFMA GEMM: f32 accumulation, the bias added in f32, one rounding to `dtype` (default: the
+    input's).  Inference only: no gradient is defined.
+    """
+    if torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)):
+        raise NotImplementedError("matmul_mxfp4 is inference-only: it defines no gradient for its input or bias "
+                                  "(call it under torch.no_grad(), or detach them)")
+    act = _mx_elem(act_format, "matmul_mxfp4")
+    _check_device(input, "matmul_mxfp4")
+    _check_device(weight, "matmul_mxfp4")
+    if weight.dim() != 2 or weight_scales.dim() != 2 or weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8:
+        raise ValueError("matmul_mxfp4: weight and weight_scales must be 2D uint8 tensors")
+    N, K = weight.shape[0], weight.shape[1] * 2
+    _mx_width(K, "matmul_mxfp4")
+    if tuple(weight_scales.shape) != (N, K // _mx_native.BLOCK):
+        raise ValueError(f"matmul_mxfp4: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: "
+                         f"expected {(N, K // _mx_native.BLOCK)}")
+    out_dtype = input.dtype if dtype is None else dtype
+    ocode = dtype_code(out_dtype, "matmul_mxfp4")
+    is_1d = input.dim() == 1
+    x = input.unsqueeze(0) if is_1d else input
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_mxfp4: input width {x.shape[-1]} does not match weight {tuple(weight.shape)} (K = {K})")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    x2 = _aligned16(x2 if x2.dtype in _native.DTYPE_CODE else x2.float())
+    M = x2.shape[0]
+    w = _aligned16(weight)
+    s = weight_scales.to(x2.device).contiguous()
+    b = None if bias is None else bias.to(x2.device).contiguous()
+    if b is not None and (b.dim() != 1 or b.shape[0] != N):
+        raise ValueError(f"matmul_mxfp4: bias {tuple(b.shape)} does not match N = {N}")
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
+    if M > 0:
+        ws_bytes = _mx_native.workspace_bytes(M, K, act)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x2.device)
+        with on_device(x2.device):
+            _mx_native.check(_mx_native.lib().mbnb_mx_linear(
+                ptr(x2), M, K, dtype_code(x2.dtype, "matmul_mxfp4"), ptr(w), ptr(s), N, act, ptr(b),
+                0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out), ocode, ptr(ws), ws_bytes, stream_ptr(x2.device)), "matmul_mxfp4")
+    out = out.reshape(*lead, N)
+    return out.squeeze(0) if is_1d else out

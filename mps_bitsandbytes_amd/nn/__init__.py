@@ -7,7 +7,8 @@ Embedding4bit / Embedding8bit -> embedding_4bit / embedding_8bit,
 SwitchBackLinear -> switchback_linear (libmbnb_train.so), Linear4bitGroup (Linear4bit layers that share their input) ->
 matmul_4bit_grouped (libmbnb_group.so), Linear4bitLoRA / Linear4bitLoRAGroup (a Linear4bit base with un-merged LoRA adapters) ->
 matmul_4bit_lora_grouped (libmbnb_lora.so), Linear4bitMultiLoRA / Linear4bitMultiLoRAGroup (a bank of adapters, one chosen per row) ->
-matmul_4bit_multilora_grouped (libmbnb_mlora.so).  `_base.py` holds what they share.
+matmul_4bit_multilora_grouped (libmbnb_mlora.so), LinearMXFP4 (an OCP MXFP4 weight on the block-scaled MFMA) -> matmul_mxfp4
+(libmbnb_mx.so).  `_base.py` holds what they share.
 """
 from .embedding import Embedding4bit, Embedding8bit, EmbeddingFP4, EmbeddingNF4
 from .linear4bit import Linear4bit, Params4bit
@@ -16,9 +17,10 @@ from .linear4bit_lora import Linear4bitLoRA, Linear4bitLoRAGroup
 from .linear4bit_multilora import Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup
 from .linear8bit import Linear8bit
 from .linear_fp8 import LinearFP8
+from .linear_mxfp4 import LinearMXFP4
 from .outlier_aware import OutlierAwareLinear
 from .switchback import SwitchBackLinear, SwitchBackLinearCallback
 
-__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'OutlierAwareLinear',
+__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'LinearMXFP4', 'OutlierAwareLinear',
                   'Embedding4bit', 'Embedding8bit', 'EmbeddingNF4', 'EmbeddingFP4',
                   'SwitchBackLinear', 'SwitchBackLinearCallback'])
