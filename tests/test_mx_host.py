@@ -1,5 +1,6 @@
 """CPU-side checks of the OCP MX format and libmbnb_mx.so, without a GPU: the numpy emulation (tests/mx_emul.py) against values
-written out by hand, the lossless generator and the exactness of every exact GEMM case that tests/test_gpu_mx.py runs, the C ABI
+written out by hand, the lossless generator and the exactness of every exact GEMM case that tests/test_gpu_mx.py runs, the forms
+tables of tests/test_gpu_mx_forms.py (exactness, coverage, the planting plan, and a mutant of the GEMM per table), the C ABI
 (loads, exports what include/mbnb_mx.h declares, argument errors as a status before any device access), and the Python surface."""
 import ctypes
 import inspect
@@ -164,6 +165,215 @@ def test_the_exact_cases_cover_every_listed_size():
     assert Ks == {32, 96, 128, 160, KS, KS + 32, 3 * KS + 32}
     assert {c[3] for c in cases.EXACT_CASES} == {"fp4", "fp8"} and len({c[4] for c in cases.EXACT_CASES}) == 3
     assert {c[5] for c in cases.EXACT_CASES} == {True, False}
+
+
+# ----------------------------------------------------------------------------- the forms tables
+def _bytes_over_nonzero_codes(codes, scales, elem):
+    """the scale bytes of the blocks that hold a non-zero element"""
+    c = emul.unpack(codes, elem)
+    live = ((c & (7 if elem == "fp4" else 0x7F)) != 0).reshape(c.shape[0], -1, 32).any(axis=2)
+    return set(np.unique(scales[live]).tolist())
+
+
+@pytest.mark.parametrize("index", range(len(cases.WIDE_CASES)))
+def test_every_wide_case_is_lossless_and_exact_in_f32(index):
+    case = cases.WIDE_CASES[index]
+    M, N, K, act, x_dtype, _, _ = case
+    x, w, w_codes, w_scales, a, c = cases.wide_operands(case, index)
+    assert (cases.to_dtype(x, x_dtype).double().numpy() == x).all()                      # the input dtype holds x
+    xc, xs = emul.quantize(x, act)
+    assert (emul.decode_f64(xc, xs, act) == x).all() and (emul.decode_f64(w_codes, w_scales, "fp4") == w).all()
+    _, qs = emul.quantize(np.where(np.abs(w) < 2.0 ** 127, w, 0), "fp4")                 # where w is an f32, the quantiser agrees
+    small = (np.abs(w).reshape(N, -1, 32).max(axis=2) < 2.0 ** 127)
+    assert (qs[small] == w_scales[small]).all()
+    unit = np.ldexp(1.0, (a[:, None] + c[None, :] - 4))
+    assert ((x[:, None, :5] * w[None, :, :5]) % unit[..., None] == 0).all()
+    total = (np.abs(x) @ np.abs(w).T) / unit
+    assert total.max() < 2.0 ** 24, total.max()                  # multiples of the unit below 2^24 of it: exact in f32 in any order
+    r = x @ w.T
+    assert (r % unit == 0).all() and (np.abs(r) < 2.0 ** 100).all() and (np.abs(r[r != 0]) > 2.0 ** -100).all()
+    assert (emul.linear_f64(xc, xs, act, w_codes, w_scales) == r).all()
+    assert (emul.gemm_as_kernel(xc, xs, act, w_codes, w_scales) == r).all()
+
+
+def test_the_wide_cases_reach_the_ends_of_the_scale_byte():
+    w_bytes, a_bytes = set(), {"fp4": set(), "fp8": set()}
+    top_code_under_254 = False
+    for index, case in enumerate(cases.WIDE_CASES):
+        x, w, w_codes, w_scales, _, _ = cases.wide_operands(case, index)
+        w_bytes |= _bytes_over_nonzero_codes(w_codes, w_scales, "fp4")
+        wc = emul.unpack(w_codes, "fp4").reshape(w.shape[0], -1, 32)
+        top_code_under_254 |= bool((((wc & 7) == 7).any(axis=2) & (w_scales == 254)).any())
+        xc, xs = emul.quantize(x, case[3])
+        a_bytes[case[3]] |= _bytes_over_nonzero_codes(xc, xs, case[3])
+        assert case[4] in (torch.float32, torch.bfloat16)
+    assert w_bytes >= {0, 1, 253, 254} and top_code_under_254, sorted(w_bytes)
+    assert 0 in a_bytes["fp4"] and max(a_bytes["fp4"]) == 252, sorted(a_bytes["fp4"])
+    assert 0 in a_bytes["fp8"] and max(a_bytes["fp8"]) == 246, sorted(a_bytes["fp8"])
+    shapes = {c[:3] for c in cases.WIDE_CASES}
+    assert shapes == {(17, 19, 256), (cases.TM + 1, cases.TN + 1, 3 * cases.KS + 64)}
+    for shape in shapes:
+        assert {(c[3], c[5], c[6]) for c in cases.WIDE_CASES if c[:3] == shape} == \
+            {(a, o, t) for a in ("fp4", "fp8") for o in (torch.float32, torch.bfloat16) for t in ("low", "high")}
+        assert {c[4] for c in cases.WIDE_CASES if c[:3] == shape} == {torch.float32, torch.bfloat16}
+
+
+@pytest.mark.parametrize("index", range(len(cases.RANGE_CASES)))
+def test_every_range_case_leaves_the_f32_range_where_it_says(index):
+    case = cases.RANGE_CASES[index]
+    name, M, N, K, a3, c, x_dtype, out_dtype = case
+    x, w, w_codes, w_scales = cases.range_operands(case, index)
+    assert (cases.to_dtype(x, x_dtype).double().numpy() == x).all()
+    for act in ("fp4", "fp8"):
+        xc, xs = emul.quantize(x, act)
+        assert (emul.decode_f64(xc, xs, act) == x).all()
+    assert (emul.decode_f64(w_codes, w_scales, "fp4") == w).all()
+    r = x @ w.T
+    assert ((r >= 0) == (np.arange(M) % 2 == 0)[:, None]).all() and (r != 0).all()      # one sign per row: partial sums are monotone
+    a = np.array([a3[i % 3] for i in range(M)])
+    unit = np.ldexp(1.0, a + c - 4)[:, None]
+    assert (r % unit == 0).all() and (np.abs(r) / unit).max() < 2.0 ** 24
+    top = np.abs(x).max(axis=1)[:, None] * np.abs(w).max(axis=1)[None, :]
+    if name == "overflow":
+        big = (a + c == 120)
+        assert big.any() and (~big).any() and top.max() < 2.0 ** 128                     # no single product overflows
+        assert (np.abs(r[big]) >= 2.0 ** 128).all() and (np.abs(r[~big]) < 2.0 ** 100).all()
+        want = cases.expected_range_output(r, out_dtype)
+        assert bool(torch.isinf(want[torch.from_numpy(big)]).all()) and bool(torch.isfinite(want[torch.from_numpy(~big)]).all())
+        assert bool((want[0] == float("inf")).all()) == bool(big[0]) and (not big[1] or bool((want[1] == float("-inf")).all()))
+    elif name == "f16-overflow":
+        assert out_dtype == torch.float16 and (np.abs(r) < 2.0 ** 100).all()
+        want = cases.expected_range_output(r, out_dtype)
+        assert bool(torch.isinf(want).any()) and bool(torch.isfinite(want).any()) and not bool(torch.isnan(want).any())
+    else:
+        assert name == "subnormal" and out_dtype == torch.float32
+        assert (np.abs(r) < 2.0 ** -126).all() and (r % 2.0 ** -149 == 0).all() and top.max() < 2.0 ** -126
+        want = cases.expected_range_output(r, out_dtype)
+        if cases.SUBNORMAL_RESULTS_KEPT:
+            assert (want.double().numpy() == r).all()
+        else:
+            assert bool((want == 0).all()) and (np.signbit(want.numpy()) == (r < 0)).all()
+
+
+@pytest.mark.parametrize("index", range(len(cases.FP8_CODE_CASES)))
+def test_fp8_code_cases_place_every_code_at_every_k_of_the_step(index):
+    case = cases.FP8_CODE_CASES[index]
+    M, N, K = case
+    x, codes, w_codes, w_scales = cases.fp8_code_operands(case)
+    assert x.dtype == np.float32 and K <= 512
+    xc, xs = emul.quantize(x, "fp8")
+    assert (xs == 127).all() and (xc == codes).all()                                      # x quantises to exactly the table's codes
+    places = cases.fp8_anchor_places(M, K)
+    k = np.arange(K)
+    anchor = (k[None, :] % 32) == np.repeat(places, 32, axis=1)
+    assert (codes[anchor] == 0x7E).all() and (anchor.reshape(M, -1, 32).sum(axis=2) == 1).all()
+    # coverage: every finite code at every k mod 128 = (low / high half, g, byte of the lane's 16), outside the anchors
+    seen = np.zeros((256, 128), dtype=bool)
+    free = ~anchor
+    seen[codes[free], np.broadcast_to(k % 128, codes.shape)[free]] = True
+    classes = {(p // 64, (p % 64) // 16, p % 16) for p in range(128)}
+    assert len(classes) == 2 * 4 * 16
+    assert seen[list(cases.E4M3_FINITE)].all() and not seen[[0x7F, 0xFF]].any()
+    assert len(cases.E4M3_FINITE) == 254 and {0x00, 0x80, 0x01, 0x81, 0x07, 0x7E, 0xFE} <= set(cases.E4M3_FINITE)
+    # every element of x meets exactly one non-zero weight, which is +-1 under byte 127
+    wd = emul.decode_f64(w_codes, w_scales, "fp4")
+    assert set(np.unique(wd)) == {-1.0, 0.0, 1.0} and ((wd != 0).sum(axis=0) == 1).all()
+    xd = x.astype(np.float64)
+    assert ((xd * 512) % 1 == 0).all() and (np.abs(xd) @ np.abs(wd).T).max() < 2.0 ** 15  # multiples of 2^-9 below 2^15: exact in any order
+    assert (emul.gemm_as_kernel(xc, xs, "fp8", w_codes, w_scales) == xd @ wd.T).all()
+
+
+def test_the_nan_plan_meets_every_place_with_every_k_block():
+    assert cases.NAN_M == cases.TM + 17 and cases.NAN_N == cases.TN + 17 and cases.NAN_K == 3 * cases.KS + 64 and cases.NAN_BLOCKS == 14
+    assert cases.NAN_PLACES == (0, 5, 15, 16, 47, 64, 100, 127, 128, cases.NAN_M - 1) and len(cases.NAN_PLAN) == 14
+    pairs, values = set(), set()
+    for run in cases.NAN_PLAN:
+        assert [p for p, _, _, _ in run] == list(cases.NAN_PLACES)
+        assert len({b for _, b, _, _ in run}) == len(run)                                 # each place in a different k block
+        for p, b, e, v in run:
+            assert 0 <= b < 14 and 0 <= e < 32
+            pairs.add((p, b))
+            values.add((b, repr(v)))
+    assert pairs == {(p, b) for p in cases.NAN_PLACES for b in range(14)}
+    assert values == {(b, repr(v)) for b in range(14) for v in cases.NAN_VALUES}          # every block, the ragged two included, sees all three
+    # the places: every fragment i, every g, both wm waves, the second tile
+    frag = {(p // cases.TM, (p % cases.TM) // 64, (p % 64) // 16, (p % 16) // 4) for p in cases.NAN_PLACES}
+    assert {f[0] for f in frag} == {0, 1} and {f[1] for f in frag} == {0, 1} and {f[2] for f in frag} == {0, 1, 2, 3} and {f[3] for f in frag} == {0, 1, 3}
+    x, w = cases.nan_operands()
+    assert (np.abs(x) @ np.abs(w).T).max() < 2.0 ** 20
+
+
+@pytest.mark.parametrize("index", range(len(cases.K64_CASES)))
+def test_every_k64_case_is_exact_in_f32(index):
+    case = cases.K64_CASES[index]
+    x, w = cases.k64_operands(case, index)
+    assert case[2] % cases.KS == 64
+    assert ((x @ w.T) % 2.0 ** -4 == 0).all() and (np.abs(x) @ np.abs(w).T).max() < 2.0 ** 20
+
+
+def test_the_k64_and_cross_tables_are_complete():
+    assert {c[2] for c in cases.K64_CASES} == {64, 192}
+    assert {(c[0], c[1]) for c in cases.K64_CASES if c[2] == 192 and c[3] == "fp8"} == {(m, n) for m in (1, 17, cases.TM + 1) for n in (1, 17, cases.TM + 1)}
+    assert len(set(cases.K64_CASES)) == len(cases.K64_CASES) == 2 * 2 * 9
+    dts = (torch.float32, torch.bfloat16, torch.float16)
+    assert set(cases.CROSS_CASES) == {(x, b, o, a) for x in dts for b in (None,) + dts for o in dts for a in ("fp4", "fp8")}
+    assert len(cases.CROSS_CASES) == 72 and cases.CROSS_SHAPE == (17, 19, 160)
+    x, w, bias = cases.cross_operands()
+    for dt in dts:
+        assert (cases.to_dtype(x, dt).double().numpy() == x).all() and (cases.to_dtype(bias, dt).double().numpy() == bias).all()
+    assert ((x @ w.T + bias) % 2.0 ** -4 == 0).all() and (np.abs(x) @ np.abs(w).T + np.abs(bias)).max() < 2.0 ** 20
+    assert {c[:2] for c in cases.RANDOM_CASES} >= {(x, x) for x in dts} and {c[3] for c in cases.RANDOM_CASES} == {"normal", "heavy"}
+    assert {g * k // 8 % 256 == 0 for g, k in cases.ABI_SHAPES} == {True, False}
+
+
+# each mutant of the GEMM fails one of the new tables; the NaN-mask and subnormal mutants pass every old exact case
+def _mutant_differs(mutate, x_codes, x_scales, act, w_codes, w_scales):
+    good = emul.linear_f64(x_codes, x_scales, act, w_codes, w_scales)
+    bad = emul.gemm_as_kernel(x_codes, x_scales, act, w_codes, w_scales, mutate=mutate)
+    return not np.array_equal(good, bad, equal_nan=True)
+
+
+def _old_exact_cases_differ(mutate):
+    out = []
+    for index, case in enumerate(cases.EXACT_CASES):
+        x, w, _ = cases.exact_operands(case, index)
+        out.append(_mutant_differs(mutate, *emul.quantize(x, case[3]), case[3], *emul.quantize(w, "fp4")))
+    return out
+
+
+def test_the_unmutated_walk_is_the_plain_product_on_the_old_cases():
+    assert not any(_old_exact_cases_differ(None))
+
+
+def test_mutant_fp8_lane_map_fails_the_code_and_wide_cases():
+    x, _, w_codes, w_scales = cases.fp8_code_operands(cases.FP8_CODE_CASES[0])
+    assert _mutant_differs("fp8_lane_map", *emul.quantize(x, "fp8"), "fp8", w_codes, w_scales)
+    x, _, w_codes, w_scales, _, _ = cases.wide_operands(cases.WIDE_CASES[0], 0)
+    assert cases.WIDE_CASES[0][3] == "fp8" and _mutant_differs("fp8_lane_map", *emul.quantize(x, "fp8"), "fp8", w_codes, w_scales)
+
+
+def test_mutant_subnormal_bit_fails_the_code_cases_and_passes_the_old_ones():
+    for case in cases.FP8_CODE_CASES:
+        x, _, w_codes, w_scales = cases.fp8_code_operands(case)
+        assert _mutant_differs("subnormal_bit", *emul.quantize(x, "fp8"), "fp8", w_codes, w_scales)
+    assert not any(_old_exact_cases_differ("subnormal_bit"))
+
+
+def test_mutant_nan_mask_fails_the_plan_and_passes_the_old_cases():
+    x, w = cases.nan_operands()
+    w_codes, w_scales = emul.quantize(w, "fp4")
+    for act in ("fp4", "fp8"):
+        xb = x.copy()
+        for p, b, e, v in cases.NAN_PLAN[0]:
+            xb[p, 32 * b + e] = v
+        assert _mutant_differs("nan_mask_fr", *emul.quantize(xb, act), act, w_codes, w_scales)
+    assert not any(_old_exact_cases_differ("nan_mask_fr"))
+
+
+def test_mutant_tail_half_fails_every_k64_case():
+    for index, case in enumerate(cases.K64_CASES):
+        x, w = cases.k64_operands(case, index)
+        assert _mutant_differs("tail_half", *emul.quantize(x, case[3]), case[3], *emul.quantize(w, "fp4")), case
 
 
 # ----------------------------------------------------------------------------- the C ABI, without a device
