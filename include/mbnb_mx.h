@@ -24,8 +24,8 @@
  * fp8 NaN code is never produced and the sign of zero is kept.  Decoding is value(code) * 2^(byte - 127), formed exactly
  * and rounded once (RNE, overflow to +-Inf) to the output dtype; byte 0xFF, and the fp8 NaN codes, give NaN.
  *
- * Alignment: x, codes, w_codes, the dequantiser's out and the workspace on 16 bytes; out and bias of mbnb_mx_linear on
- * their element size; scales need none.
+ * Alignment: x, codes, w_codes, the dequantiser's out and the workspace on 16 bytes; out and bias of mbnb_mx_linear and
+ * mbnb_mx_linear_weight_only on their element size; scales need none.
  */
 #ifndef MBNB_MX_H
 #define MBNB_MX_H
@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MBNB_MX_ABI_VERSION 1
+#define MBNB_MX_ABI_VERSION 2
 
 /* element dtypes (the values of libmbnb_hip's MBNB_F16 / MBNB_BF16 / MBNB_F32) */
 enum { MBNB_MX_F16 = 0, MBNB_MX_BF16 = 1, MBNB_MX_F32 = 2 };
@@ -52,9 +52,12 @@ enum { MBNB_MX_OK = 0, MBNB_MX_ERR_ARG = -1, MBNB_MX_ERR_SHAPE = -2, MBNB_MX_ERR
 #define MBNB_MX_TILE_N 128
 #define MBNB_MX_K_STEP 128
 
+/* k_mx_decode: the most activation rows one workgroup pass of the weight-only linear serves */
+#define MBNB_MX_DECODE_ROWS 16
+
 int mbnb_mx_abi_version(void);
 const char *mbnb_mx_last_error(void);
-/* e.g. "mx_quant fp8 + gemm_mx fp8 128x128"; "" before this thread's first launch */
+/* e.g. "mx_quant fp8 + gemm_mx fp8 128x128" or "mx_decode bf16 MT8"; "" before this thread's first launch */
 const char *mbnb_mx_last_launch(void);
 
 /* x [rows, K] of `dtype` -> codes, scales (k_mx_quantize).  rows == 0 is a no-op success. */
@@ -79,6 +82,19 @@ int64_t mbnb_mx_workspace_bytes(int64_t M, int64_t K, int act_elem);
 int mbnb_mx_linear(const void *x, int64_t M, int64_t K, int x_dtype, const void *w_codes, const void *w_scales, int64_t N,
                    int act_elem, const void *bias, int bias_dtype, void *out, int out_dtype, void *workspace,
                    int64_t workspace_bytes, void *stream);
+
+/*
+ * out[M, N] = x[M, K] . W^T + bias over the MXFP4 weight as it lies in memory, the activation NOT quantised (k_mx_decode,
+ * DESIGN.md §27).  One launch, no workspace:
+ *   out[m, n] = round( sum_b 2^(s[n, b] - 127) * ( sum_{k in block b} x[m, k] * value(code[n, k]) ) + bias[n] )
+ * with x read as f32, every sum in f32 (FMA), the scale applied to the block's partial sum, the bias added in f32 and ONE
+ * rounding to out_dtype.  A 0xFF scale byte anywhere in weight row n makes out[:, n] NaN; Inf / NaN in x propagate as IEEE
+ * arithmetic over the decoded weight does.  Any M >= 0 (M == 0: no-op success); a workgroup pass serves up to
+ * MBNB_MX_DECODE_ROWS rows (half as many f32 rows), rows beyond that run as further row chunks of the same launch, which
+ * stream the weight again.  The conventions and checks are mbnb_mx_linear's.
+ */
+int mbnb_mx_linear_weight_only(const void *x, int64_t M, int64_t K, int x_dtype, const void *w_codes, const void *w_scales,
+                               int64_t N, const void *bias, int bias_dtype, void *out, int out_dtype, void *stream);
 
 #ifdef __cplusplus
 }

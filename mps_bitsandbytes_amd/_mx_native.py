@@ -16,13 +16,14 @@ from ._native import BF16, DTYPE_CODE, F16, F32     # one definition; read from 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmbnb_mx.so")
 
-ABI_VERSION = 1            # include/mbnb_mx.h MBNB_MX_ABI_VERSION
+ABI_VERSION = 2            # include/mbnb_mx.h MBNB_MX_ABI_VERSION
 _PREFIX, _CHECK_PREFIX = "mbnb_mx", "mps_bitsandbytes_amd.mx"
 FP4, FP8 = 0, 1            # MBNB_MX_FP4 / MBNB_MX_FP8
 ELEM_CODE = {"fp4": FP4, "fp8": FP8}
 ERR_ARG, ERR_SHAPE, ERR_WORKSPACE = -1, -2, -3
 BLOCK = 32                 # elements per scale byte
 TM, TN, KS = 128, 128, 128  # MBNB_MX_TILE_M / _TILE_N / _K_STEP: k_gemm_mx's workgroup tile and K-step
+DECODE_ROWS = 16           # MBNB_MX_DECODE_ROWS: the most activation rows of one k_mx_decode workgroup pass
 NAN_SCALE = 0xFF
 
 _SIGNATURES = {
@@ -34,6 +35,8 @@ _SIGNATURES = {
     "mbnb_mx_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
     "mbnb_mx_linear": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int,
                                c_void_p, c_int64, c_void_p]),
+    "mbnb_mx_linear_weight_only": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int,
+                                           c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -7,6 +7,9 @@
 //   k_gemm_mx        out[M, N] = A . W^T + bias over the codes and scale bytes of both operands as they lie in memory:
 //                    v_mfma_scale_f32_16x16x128_f8f6f4, whose lane holds the scale byte of one MX block (32 k of one row).
 //                    128 x 128 output tile, 4 waves of 64 x 64, K-step 128, two LDS stages filled by 16-byte LDS-DMA.
+//   k_mx_decode      the weight-only linear for decode steps: the activation stays in its dtype, the codes and
+//                    scale bytes are streamed once and decoded in registers, one lane per MX block, f32 FMA (one 16-bit row, f32 rows);
+//   k_mx_decode_mfma the same for 2 and more bf16 / f16 rows on v_mfma_f32_16x16x32, whose K is one MX block.
 #include "../../include/mbnb_mx.h"
 #include "host.h"
 
@@ -325,6 +328,287 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
     }
 }
 
+// ---------------------------------------------------------------- the weight-only decode linear
+// out[m, n] = sum_b 2^(s[n, b] - 127) * (sum_{k in block b} x[m, k] * v(code[n, k])) + bias[n]: the activation is NOT quantised.
+// One lane owns one MX block of a weight row per pass: 16 bytes of codes (one dwordx4) and one scale byte, so a wave covers
+// kDecodeChunk = 2048 k of a row, 1 KiB of codes, coalesced.  A wave runs RW weight rows against one read of the activations, a
+// workgroup 4 RW rows against one staging of them: the workgroup copies its MT rows x 2048 k of x into LDS per pass (zeros for
+// the rows past M and the k past K), lane l's 32 values of a row as S 16-byte slots at slot (row * 64 + l) * S + (j ^ swz(l)).
+// The XOR spreads the 16 lanes of every ds_read_b128 lane group over the 16 slots of the 256-byte bank row, so the per-lane
+// 64- / 128-byte reads are conflict-free.  The 32 products of a block go into one partial sum per activation row (f32 FMA; a
+// product of a 16-bit x and an E2M1 value is exact), which is multiplied by the block's scale ONCE and added to the lane's
+// accumulator: an element that alone is no f32 (code 6 under byte 254) never exists.  A 0xFF byte anywhere in the row makes the
+// whole column NaN, whatever x holds.  DPP wave sums; lane 63 adds the bias and stores with one rounding.  This FMA form serves ONE
+// 16-bit row (MT 1) and every call with f32 rows (MT 1, 2, 4, 8: 64 KiB of LDS at 8); 2 and more 16-bit rows take
+// k_mx_decode_mfma below.
+constexpr int kDecodeChunk = 2048;
+constexpr int decode_rw(int mt) { return mt == 1 ? 1 : (mt <= 4 ? 2 : 4); }      // weight rows per wave
+static_assert(MBNB_MX_DECODE_ROWS == 16, "the MFMA form's 16 x 16 tile and the MT dispatch below");
+
+// nibble E of w -> the E2M1 value: the code's three magnitude bits placed at f32 bits 22..24 are 2^-126 times the value (codes 0
+// and 1 as the subnormals 0 and 2^-127), so one exact multiplication by 2^126 finishes the decode
+template <int E> __device__ __forceinline__ float dec_nibble(uint32_t w) {
+    const uint32_t t = 4 * E <= 22 ? w << (22 - 4 * E > 0 ? 22 - 4 * E : 0) : w >> (4 * E - 22 > 0 ? 4 * E - 22 : 0);
+    const uint32_t bits = (t & 0x01C00000u) | ((w << (28 - 4 * E)) & 0x80000000u);
+    return __uint_as_float(bits) * 0x1p126f;
+}
+
+__device__ __forceinline__ void decode8(uint32_t w, float v[8]) {
+    v[0] = dec_nibble<0>(w), v[1] = dec_nibble<1>(w), v[2] = dec_nibble<2>(w), v[3] = dec_nibble<3>(w);
+    v[4] = dec_nibble<4>(w), v[5] = dec_nibble<5>(w), v[6] = dec_nibble<6>(w), v[7] = dec_nibble<7>(w);
+}
+
+// lane 63 ends with the sum over the wave: row shifts inside the rows of 16, then the row broadcasts
+__device__ __forceinline__ float decode_wave_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xF, 0xF, true));   // row_shr:1
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xF, 0xF, true));   // row_shr:2
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xF, 0xF, true));   // row_shr:4
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xF, 0xF, true));   // row_shr:8
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, true));   // row_bcast:15
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, true));   // row_bcast:31
+    return v;
+}
+
+__device__ __forceinline__ void store_out(void *out, int dtype, int64_t i, float v) {
+    if (dtype == MBNB_MX_F32) ((float *)out)[i] = v;
+    else if (dtype == MBNB_MX_BF16) ((bf16_t *)out)[i] = (bf16_t)v;
+    else ((f16_t *)out)[i] = (f16_t)v;
+}
+
+template <typename T, int MT>
+__global__ __launch_bounds__(kThreads) void k_mx_decode(const T *__restrict__ x, const uint8_t *__restrict__ W, const uint8_t *__restrict__ Ws,
+                                                        int64_t M, int64_t N, int64_t K, const void *__restrict__ bias, int bias_dtype,
+                                                        void *__restrict__ out, int out_dtype, int row_chunks) {
+    constexpr int RW = decode_rw(MT);
+    constexpr int S = 32 * (int)sizeof(T) / 16;              // 16-byte slots of a lane's 32 activations: 4 (16 bit) or 8 (f32)
+    constexpr int UNITS = 64 * S;                            // slots of one activation row of a pass
+    constexpr int PER = 16 / (int)sizeof(T);                 // activations per slot
+    static_assert(MT * UNITS * 16 <= 65536 && (MT * UNITS) % kThreads == 0, "the staged rows fit 64 KiB of LDS");
+    __shared__ __attribute__((aligned(16))) uint8_t xs[MT * UNITS * 16];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t m0 = (int64_t)(blockIdx.x % row_chunks) * MT;
+    const int64_t n0 = (int64_t)(blockIdx.x / row_chunks) * (4 * RW) + wave * RW;
+    const int64_t KB = K / 32, ldw = K / 2;
+    const int swz = (lane / (16 / S)) & (S - 1);
+
+    const uint8_t *w_row[RW], *s_row[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        const int64_t n = n0 + r < N ? n0 + r : N - 1;       // a row past N reads the last row and stores nothing
+        w_row[r] = W + n * ldw;
+        s_row[r] = Ws + n * KB;
+    }
+    float acc[RW][MT];
+    bool ff[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        ff[r] = false;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[r][m] = 0.0f;
+    }
+
+    for (int64_t k0 = 0; k0 < K; k0 += kDecodeChunk) {
+        if (k0) __syncthreads();                             // every wave is done with the last pass's activations
+        const int64_t blk = k0 / 32 + lane;
+        const bool live = blk < KB;
+        v4i wq[RW];
+        uint32_t sb[RW];
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            wq[r] = live ? __builtin_nontemporal_load((const v4i *)(w_row[r] + blk * 16)) : v4i{0, 0, 0, 0};
+            sb[r] = live ? (uint32_t)s_row[r][blk] : (uint32_t)kOneScale;
+        }
+#pragma unroll
+        for (int it = 0; it < MT * UNITS / kThreads; ++it) {
+            const int u = it * kThreads + tid, row = u / UNITS, c = u % UNITS;
+            const int64_t k = k0 + (int64_t)c * PER;
+            v4i v = v4i{0, 0, 0, 0};
+            if (m0 + row < M && k < K) v = *(const v4i *)(x + (m0 + row) * K + k);
+            const int l = c / S, j = c % S;
+            *(v4i *)(xs + ((row * 64 + l) * S + (j ^ ((l / (16 / S)) & (S - 1)))) * 16) = v;
+        }
+        __syncthreads();
+
+        float p[RW][MT];
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int m = 0; m < MT; ++m) p[r][m] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                        // dword q of the codes: the block's k 8 q .. 8 q + 7
+            float wv[RW][8];
+#pragma unroll
+            for (int r = 0; r < RW; ++r) decode8((uint32_t)wq[r][q], wv[r]);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                float xv[8];
+                const uint8_t *base = xs + (m * 64 + lane) * S * 16;
+                if constexpr (sizeof(T) == 2) {
+                    typedef T tvec __attribute__((ext_vector_type(8)));
+                    const tvec t = *(const tvec *)(base + ((q ^ swz) * 16));
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xv[e] = (float)t[e];
+                } else {
+                    const float4 a = *(const float4 *)(base + (((2 * q) ^ swz) * 16)), b = *(const float4 *)(base + (((2 * q + 1) ^ swz) * 16));
+                    xv[0] = a.x, xv[1] = a.y, xv[2] = a.z, xv[3] = a.w, xv[4] = b.x, xv[5] = b.y, xv[6] = b.z, xv[7] = b.w;
+                }
+#pragma unroll
+                for (int r = 0; r < RW; ++r)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) p[r][m] = __builtin_fmaf(xv[e], wv[r][e], p[r][m]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            ff[r] |= sb[r] == (uint32_t)kNaNScale;
+            const float sv = scale_value(sb[r] == (uint32_t)kNaNScale ? (uint32_t)kOneScale : sb[r]);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[r][m] = __builtin_fmaf(p[r][m], sv, acc[r][m]);
+        }
+    }
+
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        const bool col_nan = __ballot(ff[r]) != 0;           // a 0xFF byte anywhere in weight row n: the column is NaN
+        const int64_t n = n0 + r;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const float s = decode_wave_sum(acc[r][m]);
+            if (lane == 63 && n < N && m0 + m < M) {
+                const float v = s + (bias ? load_bias(bias, bias_dtype, n) : 0.0f);
+                store_out(out, out_dtype, (m0 + m) * N + n, col_nan ? __uint_as_float(0x7FC00000u) : v);
+            }
+        }
+    }
+}
+
+// k_mx_decode_mfma: 2 to 16 rows of 16-bit activations on v_mfma_f32_16x16x32_{bf16,f16}, whose K = 32 is one MX block.  A workgroup
+// of 8 waves owns 16 weight rows and ALL of K: wave w takes the k-steps w, w + 8, ... of 4 blocks (128 k) each, and the eight
+// accumulators are added through LDS at the end, in wave order; the loads of two k-steps are requested before the first is used.
+// (Two tiles of 16 weight rows per workgroup, every x fragment feeding two MFMAs, measured slower at 11008 rows: DESIGN.md §27.)
+// Per k-step lane (n = l & 15, g = l >> 4) fetches the 16 bytes of
+// block 4 c + g of weight row n (a wave reads 64 consecutive bytes of each of its 16 rows) and a 4 x 4 transpose across the four
+// lane groups (two v_permlane32_swap, two v_permlane16_swap) leaves in register q the dword g of block 4 c + q: the B fragment
+// B[k = 8 g + j][column n] of the MFMA of block q.  Its 8 codes become 16-bit values by byte lookups (v_perm_b32 over the 8
+// magnitudes' high and low bytes, the sign OR-ed into the high byte).  The A fragment A[row m = l & 15][k = 8 g + j] is 16 bytes of x
+// straight from memory (rows past M and k past K as zeros, never read).  D (column n on the lane, rows 4 g + r) is the block's
+// partial sum: 4 FMAs by the lane's scale 2^(s[n, block] - 127) add it to the accumulators.
+constexpr int kMfmaWaves = 8;
+
+template <typename T> struct E2M1Bytes;      // the 16-bit patterns of 0, .5, 1, 1.5, 2, 3, 4, 6 as byte tables: {codes 4..7, codes 0..3}
+template <> struct E2M1Bytes<bf16_t> { static constexpr uint32_t hi[2] = {0x40404040u, 0x3F3F3F00u}, lo[2] = {0xC0804000u, 0xC0800000u}; };
+template <> struct E2M1Bytes<f16_t> { static constexpr uint32_t hi[2] = {0x46444240u, 0x3E3C3800u}, lo[2] = {0u, 0u}; };
+
+// the 8 codes of w (k = 0 .. 7, the lower k in the lower nibble) -> 8 values of T, k ascending
+template <typename T> __device__ __forceinline__ v4i decode8_16(uint32_t w) {
+    const uint32_t sel_e = w & 0x07070707u, sel_o = (w >> 4) & 0x07070707u;                       // k = 0, 2, 4, 6 and 1, 3, 5, 7
+    const uint32_t hi_e = __builtin_amdgcn_perm(E2M1Bytes<T>::hi[0], E2M1Bytes<T>::hi[1], sel_e) | ((w << 4) & 0x80808080u);
+    const uint32_t hi_o = __builtin_amdgcn_perm(E2M1Bytes<T>::hi[0], E2M1Bytes<T>::hi[1], sel_o) | (w & 0x80808080u);
+    const uint32_t lo_e = __builtin_amdgcn_perm(E2M1Bytes<T>::lo[0], E2M1Bytes<T>::lo[1], sel_e);
+    const uint32_t lo_o = __builtin_amdgcn_perm(E2M1Bytes<T>::lo[0], E2M1Bytes<T>::lo[1], sel_o);
+    const uint32_t e01 = __builtin_amdgcn_perm(hi_e, lo_e, 0x05010400u), e23 = __builtin_amdgcn_perm(hi_e, lo_e, 0x07030602u);   // k 0, 2 | 4, 6
+    const uint32_t o01 = __builtin_amdgcn_perm(hi_o, lo_o, 0x05010400u), o23 = __builtin_amdgcn_perm(hi_o, lo_o, 0x07030602u);   // k 1, 3 | 5, 7
+    return v4i{(int)__builtin_amdgcn_perm(o01, e01, 0x05040100u), (int)__builtin_amdgcn_perm(o01, e01, 0x07060302u),
+               (int)__builtin_amdgcn_perm(o23, e23, 0x05040100u), (int)__builtin_amdgcn_perm(o23, e23, 0x07060302u)};
+}
+
+__device__ __forceinline__ v4f mfma16(v4i a, v4i b, bf16_t) {
+    typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+}
+__device__ __forceinline__ v4f mfma16(v4i a, v4i b, f16_t) {
+    typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * kMfmaWaves) void k_mx_decode_mfma(const T *__restrict__ x, const uint8_t *__restrict__ W,
+                                                                     const uint8_t *__restrict__ Ws, int64_t M, int64_t N, int64_t K,
+                                                                     const void *__restrict__ bias, int bias_dtype, void *__restrict__ out,
+                                                                     int out_dtype, int row_chunks) {
+    static_assert(sizeof(T) == 2, "16-bit activations");
+    constexpr int U = 2;                                     // k-steps whose loads are requested before the first of them is used
+    __shared__ float red[kMfmaWaves][4][64];
+    __shared__ int red_ff[kMfmaWaves][64];
+    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t m0 = (int64_t)(blockIdx.x % row_chunks) * MBNB_MX_DECODE_ROWS;
+    const int64_t n0 = (int64_t)(blockIdx.x / row_chunks) * 16;
+    const int64_t KB = K / 32, ldw = K / 2, last = KB - 1;
+    const int64_t n = n0 + fr < N ? n0 + fr : N - 1;         // a column past N reads the last weight row and stores nothing
+    const uint8_t *w_row = W + n * ldw, *s_row = Ws + n * KB;
+    const bool x_live = m0 + fr < M;
+    const T *x_row = x + (x_live ? m0 + fr : 0) * K + 8 * g;
+
+    v4f acc = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    bool ff = false;
+    const int64_t steps = (KB + 3) / 4;
+    for (int64_t c0 = wave; c0 < steps; c0 += kMfmaWaves * U) {
+        // every load is unconditional, from a clamped (valid) address; what lies past K or M becomes zeros in registers
+        v4i wq[U], xa[U][4];
+        uint32_t sb[U][4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t c = c0 + u * kMfmaWaves, blk = 4 * c + g;
+            wq[u] = __builtin_nontemporal_load((const v4i *)(w_row + (blk < KB ? blk : last) * 16));
+            if (blk >= KB) wq[u] = v4i{0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool in = 4 * c + q < KB;
+                const int64_t b = in ? 4 * c + q : last;
+                sb[u][q] = s_row[b];
+                if (!in) sb[u][q] = (uint32_t)kOneScale;
+                xa[u][q] = *(const v4i *)(x_row + b * 32);
+                if (!(in && x_live)) xa[u][q] = v4i{0, 0, 0, 0};
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (c0 + u * kMfmaWaves >= steps) break;         // wave-uniform
+            // register q of lane group g holds dword q of block g; after the transpose, dword g of block q
+            typedef unsigned v2u __attribute__((ext_vector_type(2)));
+            const v2u s02 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][0], (unsigned)wq[u][2], false, false);
+            const v2u s13 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][1], (unsigned)wq[u][3], false, false);
+            const v2u t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
+            const v2u t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
+            const uint32_t wb[4] = {t01[0], t01[1], t23[0], t23[1]};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const v4f d = mfma16(xa[u][q], decode8_16<T>(wb[q]), T{});
+                const uint32_t byte = sb[u][q];
+                ff |= byte == (uint32_t)kNaNScale;
+                const float sv = scale_value(byte == (uint32_t)kNaNScale ? (uint32_t)kOneScale : byte);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(d[r], sv, acc[r]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][r][lane] = acc[r];
+    red_ff[wave][lane] = ff;
+    __syncthreads();
+    if (wave == 0) {                                         // the eight partial sums, in wave order
+        bool col_nan = false;
+        v4f s = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int w = 0; w < kMfmaWaves; ++w) {
+            col_nan |= red_ff[w][lane] != 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[r] += red[w][r][lane];
+        }
+        if (n0 + fr < N) {
+            const float b = bias ? load_bias(bias, bias_dtype, n) : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t m = m0 + 4 * g + r;
+                if (m < M) store_out(out, out_dtype, m * N + n, col_nan ? __uint_as_float(0x7FC00000u) : s[r] + b);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- host side
 const char *elem_name(int elem) { return elem == MBNB_MX_FP4 ? "fp4" : "fp8"; }
 bool known_dtype(int d) { return d >= MBNB_MX_F16 && d <= MBNB_MX_F32; }
@@ -361,6 +645,43 @@ int launch_gemm(const uint8_t *A, const uint8_t *As, const void *W, const void *
     hipLaunchKernelGGL((k_gemm_mx<AELEM, TO>), dim3((unsigned)(tiles_m * tiles_n)), dim3(kThreads), 0, s, A, As, (const uint8_t *)W,
                        (const uint8_t *)Ws, M, N, K, bias, bias_dtype, (TO *)out, (int)tiles_m);
     return mbnb::launch_status("k_gemm_mx");
+}
+
+// the activation rows of one pass of the FMA form: the power of two that holds M, up to kDecodeFmaRows (f32 rows: 64 KiB of LDS)
+constexpr int kDecodeFmaRows = MBNB_MX_DECODE_ROWS / 2;
+int decode_rows(int64_t M) {
+    int mt = 1;
+    while (mt < M && mt < kDecodeFmaRows) mt *= 2;
+    return mt;
+}
+// 2 rows and more of 16-bit activations take the MFMA form: 16 weight rows per workgroup, 16 activation rows per pass
+bool decode_mfma(int64_t M, int x_dtype) { return M >= 2 && x_dtype != MBNB_MX_F32; }
+int64_t decode_grid(int64_t M, int64_t N, int mt, bool mfma) {
+    if (mfma) return ((N + 15) / 16) * ((M + MBNB_MX_DECODE_ROWS - 1) / MBNB_MX_DECODE_ROWS);
+    const int rows = 4 * decode_rw(mt);
+    return ((N + rows - 1) / rows) * ((M + mt - 1) / mt);
+}
+
+template <typename T>
+int launch_decode_mfma(const void *x, const void *W, const void *Ws, int64_t M, int64_t N, int64_t K, const void *bias, int bias_dtype,
+                       void *out, int out_dtype, hipStream_t s) {
+    if constexpr (sizeof(T) != 2) {
+        return fail(MBNB_MX_ERR_ARG, "k_mx_decode_mfma: 16-bit activations only");
+    } else {
+        const int chunks = (int)((M + MBNB_MX_DECODE_ROWS - 1) / MBNB_MX_DECODE_ROWS);
+        const dim3 grid((unsigned)decode_grid(M, N, MBNB_MX_DECODE_ROWS, true)), block(64 * kMfmaWaves);
+        hipLaunchKernelGGL((k_mx_decode_mfma<T>), grid, block, 0, s, (const T *)x, (const uint8_t *)W, (const uint8_t *)Ws, M, N, K, bias,
+                           bias_dtype, out, out_dtype, chunks);
+        return mbnb::launch_status("k_mx_decode_mfma");
+    }
+}
+
+template <typename T, int MT>
+int launch_decode(const void *x, const void *W, const void *Ws, int64_t M, int64_t N, int64_t K, const void *bias, int bias_dtype, void *out,
+                  int out_dtype, hipStream_t s) {
+    hipLaunchKernelGGL((k_mx_decode<T, MT>), dim3((unsigned)decode_grid(M, N, MT, false)), dim3(kThreads), 0, s, (const T *)x, (const uint8_t *)W,
+                       (const uint8_t *)Ws, M, N, K, bias, bias_dtype, out, out_dtype, (int)((M + MT - 1) / MT));
+    return mbnb::launch_status("k_mx_decode");
 }
 
 }  // namespace
@@ -447,6 +768,46 @@ int mbnb_mx_linear(const void *x, int64_t M, int64_t K, int x_dtype, const void 
     });
     if (st == 0)
         snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, "mx_quant %s + gemm_mx %s %dx%d", elem_name(act_elem), elem_name(act_elem), TM, TN);
+    return st;
+}
+
+int mbnb_mx_linear_weight_only(const void *x, int64_t M, int64_t K, int x_dtype, const void *w_codes, const void *w_scales, int64_t N,
+                               const void *bias, int bias_dtype, void *out, int out_dtype, void *stream) {
+    if (!known_dtype(x_dtype) || !known_dtype(out_dtype) || (bias && !known_dtype(bias_dtype)))
+        return fail(MBNB_MX_ERR_ARG, "mbnb_mx_linear_weight_only: unknown dtype (x %d, bias %d, out %d)", x_dtype, bias_dtype, out_dtype);
+    if (const int st = check_shape("mbnb_mx_linear_weight_only", M, K)) return st;
+    if (N <= 0 || N > mbnb::kMaxElems / K || (M > 0 && N > mbnb::kMaxElems / M))
+        return fail(MBNB_MX_ERR_SHAPE, "mbnb_mx_linear_weight_only: N = %lld", (long long)N);
+    if (M == 0) return 0;
+    const bool mfma = decode_mfma(M, x_dtype);
+    const int mt = mfma ? MBNB_MX_DECODE_ROWS : decode_rows(M);
+    const int64_t groups = decode_grid(M, N, mt, mfma);
+    if (groups > INT32_MAX)
+        return fail(MBNB_MX_ERR_SHAPE, "mbnb_mx_linear_weight_only: %lld workgroups exceed one launch", (long long)groups);
+    if (!x || !w_codes || !w_scales || !out) return fail(MBNB_MX_ERR_ARG, "mbnb_mx_linear_weight_only: NULL x, w_codes, w_scales or out");
+    if (!mbnb::aligned(x, 16) || !mbnb::aligned(w_codes, 16))
+        return fail(MBNB_MX_ERR_ARG, "mbnb_mx_linear_weight_only: misaligned x or w_codes (16 bytes each)");
+    if (!mbnb::aligned(out, mbnb::esize(out_dtype)) || (bias && !mbnb::aligned(bias, mbnb::esize(bias_dtype))))
+        return fail(MBNB_MX_ERR_ARG, "mbnb_mx_linear_weight_only: misaligned out or bias (the element size each)");
+    hipStream_t s = (hipStream_t)stream;
+    const int st = mbnb::with_dtype(x_dtype, [&](auto t) {
+        using T = decltype(t);
+        if (mfma) return launch_decode_mfma<T>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+        if constexpr (sizeof(T) == 2) {
+            return launch_decode<T, 1>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+        } else {
+            switch (mt) {
+                case 1: return launch_decode<T, 1>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+                case 2: return launch_decode<T, 2>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+                case 4: return launch_decode<T, 4>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+                default: return launch_decode<T, 8>(x, w_codes, w_scales, M, N, K, bias, bias_dtype, out, out_dtype, s);
+            }
+        }
+    });
+    if (st == 0) {
+        const char *names[] = {"f16", "bf16", "f32"};
+        snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, mfma ? "mx_decode_mfma %s MT%d" : "mx_decode %s MT%d", names[x_dtype], mt);
+    }
     return st;
 }
 

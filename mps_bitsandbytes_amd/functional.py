@@ -1914,11 +1914,19 @@ def matmul_mxfp4(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Opt
     the MX quantiser of the activation rows to `act_format` ("fp8": E4M3, "fp4": E2M1).  Two launches: the quantiser into a
     workspace, then the block-scaled MFMA GEMM: f32 accumulation, the bias added in f32, one rounding to `dtype` (default: the
     input's).  Inference only: no gradient is defined.
+
+    ``act_format="none"`` is the weight-only form for decode steps: the activation is NOT quantised, it stays in
+    its own dtype, and one launch of `k_mx_decode` streams the codes and scale bytes once and decodes them in registers (no
+    workspace; f32 accumulation with the scale applied per block, the bias added in f32, one rounding).  Any number of rows
+    takes that launch, with one exception: bf16 in and out (and bias) with more than 16 rows, ``K % 64 == 0`` and ``K >= 128`` run the
+    composed form ``linear_dense(x, dequantize_mx(w, s, "fp4", torch.bfloat16), bias)``, i.e. a dequantise launch (exact in
+    bf16 for every scale byte) and the dense bf16 GEMM.  The two routes differ in summation order only.
     """
     if torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)):
         raise NotImplementedError("matmul_mxfp4 is inference-only: it defines no gradient for its input or bias "
                                   "(call it under torch.no_grad(), or detach them)")
-    act = _mx_elem(act_format, "matmul_mxfp4")
+    weight_only = isinstance(act_format, str) and act_format == "none"
+    act = None if weight_only else _mx_elem(act_format, "matmul_mxfp4")
     _check_device(input, "matmul_mxfp4")
     _check_device(weight, "matmul_mxfp4")
     if weight.dim() != 2 or weight_scales.dim() != 2 or weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8:
@@ -1945,8 +1953,19 @@ def matmul_mxfp4(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Opt
         raise ValueError(f"matmul_mxfp4: bias {tuple(b.shape)} does not match N = {N}")
     if b is not None and b.dtype not in _native.DTYPE_CODE:
         b = b.float()
+    if (weight_only and M > _mx_native.DECODE_ROWS and x2.dtype == torch.bfloat16 and out_dtype == torch.bfloat16
+            and K % 64 == 0 and K >= 128 and (b is None or b.dtype == torch.bfloat16)):
+        # prefill-sized bf16 calls: dequantise (exact in bf16) + the dense GEMM; the same sum in another order
+        out = linear_dense(x2, dequantize_mx(w, s, "fp4", torch.bfloat16), b)
+        out = out.reshape(*lead, N)
+        return out.squeeze(0) if is_1d else out
     out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
-    if M > 0:
+    if M > 0 and weight_only:
+        with on_device(x2.device):
+            _mx_native.check(_mx_native.lib().mbnb_mx_linear_weight_only(
+                ptr(x2), M, K, dtype_code(x2.dtype, "matmul_mxfp4"), ptr(w), ptr(s), N, ptr(b),
+                0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out), ocode, stream_ptr(x2.device)), "matmul_mxfp4")
+    elif M > 0:
         ws_bytes = _mx_native.workspace_bytes(M, K, act)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x2.device)
         with on_device(x2.device):

@@ -4,6 +4,8 @@ LinearMXFP4 — a linear layer whose weight is OCP MXFP4 (E2M1 codes, one E8M0 s
 No counterpart in the reference.  Buffers `weight` uint8 [N, K / 2] (even k in the low nibble) and `weight_scales` uint8
 [N, K / 32], both row-major: the tensors MXFP4 checkpoints ship.  The forward is `functional.matmul_mxfp4`: the
 activation rows are quantised to `act_format` ("fp8": E4M3, "fp4": E2M1) and the product runs on gfx950's block-scaled MFMA.
+`act_format="none"` is the weight-only form for token generation: the activation is not quantised, and one launch streams and
+decodes the weight (bf16 calls of more than 16 rows run dequantise + the dense GEMM instead; the same sum in another order).
 Inference only: an input or a bias that requires grad, with grad enabled, raises NotImplementedError.
 """
 from typing import Optional
@@ -25,8 +27,8 @@ class LinearMXFP4(QuantizedModule):
         super().__init__()
         if in_features <= 0 or in_features % _BLOCK:
             raise ValueError(f"LinearMXFP4: in_features ({in_features}) must be a positive multiple of the MX block, {_BLOCK}")
-        if act_format not in ("fp4", "fp8"):
-            raise ValueError(f"LinearMXFP4: unknown act_format {act_format!r} (supported: 'fp4', 'fp8')")
+        if act_format not in ("fp4", "fp8", "none"):
+            raise ValueError(f"LinearMXFP4: unknown act_format {act_format!r} (supported: 'fp4', 'fp8', 'none')")
         self._init_linear(in_features, out_features, compute_dtype)
         self.act_format = act_format
         self.register_buffer('weight', torch.zeros(out_features, in_features // 2, dtype=torch.uint8, device=device))
@@ -41,7 +43,7 @@ class LinearMXFP4(QuantizedModule):
     @classmethod
     def from_linear(cls, linear: nn.Linear, act_format: str = "fp8", device=None,
                     compute_dtype: Optional[torch.dtype] = None) -> 'LinearMXFP4':
-        """Quantise an nn.Linear on `device` with the HIP quantiser."""
+        """Quantise an nn.Linear on `device` with the HIP quantiser; `act_format` as in the constructor ("none": weight-only)."""
         device = source_device(linear.weight, device)
         wdtype = linear.weight.dtype
         cd = compute_dtype if compute_dtype is not None else (wdtype if wdtype in (torch.float16, torch.bfloat16, torch.float32) else torch.bfloat16)
