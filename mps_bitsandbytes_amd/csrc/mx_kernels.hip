@@ -12,6 +12,7 @@
 //   k_mx_decode_mfma the same for 2 and more bf16 / f16 rows on v_mfma_f32_16x16x32, whose K is one MX block.
 #include "../../include/mbnb_mx.h"
 #include "host.h"
+#include "mx_decode.h"
 
 static_assert(MBNB_MX_F16 == mbnb::kF16 && MBNB_MX_BF16 == mbnb::kBF16 && MBNB_MX_F32 == mbnb::kF32, "host.h's dtype codes");
 
@@ -20,14 +21,21 @@ namespace {
 using mbnb::bf16_t;
 using mbnb::f16_t;
 using mbnb::fail;
+// the scale, the byte-table decode, the MFMA of one block, the bias load and the output store: mx_decode.h, shared with moe_kernels.hip
+using mbnb::mx::v4i;
+using mbnb::mx::v4f;
+using mbnb::mx::kNaNScale;
+using mbnb::mx::kOneScale;
+using mbnb::mx::kMfmaWaves;
+using mbnb::mx::scale_value;
+using mbnb::mx::load_bias;
+using mbnb::mx::store_out;
+using mbnb::mx::decode8_16;
+using mbnb::mx::mfma16;
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;          // every launch: 4 waves
-constexpr int kNaNScale = 0xFF;        // E8M0: the block is NaN
-constexpr int kOneScale = 127;         // E8M0: 2^0
 
 // ---------------------------------------------------------------- the element formats
 // |a| -> E2M1 code 0..7 (0, .5, 1, 1.5, 2, 3, 4, 6), nearest, ties to the even code, everything above 5 to 6
@@ -59,9 +67,6 @@ __device__ __forceinline__ float dec_e4m3(uint32_t c) {
     if (e == 0u) return __uint_as_float(__float_as_uint((float)m * 0.001953125f) | sign);    // m * 2^-9
     return __uint_as_float(((e + 120u) << 23) | (m << 20) | sign);
 }
-
-// 2^(byte - 127) for byte 0..254; byte 0 is the f32 subnormal 2^-127
-__device__ __forceinline__ float scale_value(uint32_t byte) { return __uint_as_float(byte ? byte << 23 : 0x00400000u); }
 
 template <typename T> __device__ __forceinline__ void load8(const T *p, float v[8]) {
     typedef T tvec __attribute__((ext_vector_type(8)));
@@ -171,12 +176,6 @@ __global__ __launch_bounds__(kThreads) void k_mx_dequantize(const uint8_t *__res
 // bytes instead; the k blocks past K are zeroed in registers on the last K-step, the rows past the operand are never stored.
 constexpr int TM = MBNB_MX_TILE_M, TN = MBNB_MX_TILE_N, KS = MBNB_MX_K_STEP;
 static_assert(TM == 128 && TN == 128 && KS == 128, "the wave grid and the chunk maps below are written for 128 x 128 x 128");
-
-__device__ __forceinline__ float load_bias(const void *bias, int dtype, int64_t col) {
-    if (dtype == MBNB_MX_F32) return ((const float *)bias)[col];
-    if (dtype == MBNB_MX_BF16) return (float)((const bf16_t *)bias)[col];
-    return (float)((const f16_t *)bias)[col];
-}
 
 template <int AELEM, typename TO>
 __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict__ A, const uint8_t *__restrict__ As,
@@ -369,12 +368,6 @@ __device__ __forceinline__ float decode_wave_sum(float v) {
     return v;
 }
 
-__device__ __forceinline__ void store_out(void *out, int dtype, int64_t i, float v) {
-    if (dtype == MBNB_MX_F32) ((float *)out)[i] = v;
-    else if (dtype == MBNB_MX_BF16) ((bf16_t *)out)[i] = (bf16_t)v;
-    else ((f16_t *)out)[i] = (f16_t)v;
-}
-
 template <typename T, int MT>
 __global__ __launch_bounds__(kThreads) void k_mx_decode(const T *__restrict__ x, const uint8_t *__restrict__ W, const uint8_t *__restrict__ Ws,
                                                         int64_t M, int64_t N, int64_t K, const void *__restrict__ bias, int bias_dtype,
@@ -494,35 +487,8 @@ __global__ __launch_bounds__(kThreads) void k_mx_decode(const T *__restrict__ x,
 // B[k = 8 g + j][column n] of the MFMA of block q.  Its 8 codes become 16-bit values by byte lookups (v_perm_b32 over the 8
 // magnitudes' high and low bytes, the sign OR-ed into the high byte).  The A fragment A[row m = l & 15][k = 8 g + j] is 16 bytes of x
 // straight from memory (rows past M and k past K as zeros, never read).  D (column n on the lane, rows 4 g + r) is the block's
-// partial sum: 4 FMAs by the lane's scale 2^(s[n, block] - 127) add it to the accumulators.
-constexpr int kMfmaWaves = 8;
-
-template <typename T> struct E2M1Bytes;      // the 16-bit patterns of 0, .5, 1, 1.5, 2, 3, 4, 6 as byte tables: {codes 4..7, codes 0..3}
-template <> struct E2M1Bytes<bf16_t> { static constexpr uint32_t hi[2] = {0x40404040u, 0x3F3F3F00u}, lo[2] = {0xC0804000u, 0xC0800000u}; };
-template <> struct E2M1Bytes<f16_t> { static constexpr uint32_t hi[2] = {0x46444240u, 0x3E3C3800u}, lo[2] = {0u, 0u}; };
-
-// the 8 codes of w (k = 0 .. 7, the lower k in the lower nibble) -> 8 values of T, k ascending
-template <typename T> __device__ __forceinline__ v4i decode8_16(uint32_t w) {
-    const uint32_t sel_e = w & 0x07070707u, sel_o = (w >> 4) & 0x07070707u;                       // k = 0, 2, 4, 6 and 1, 3, 5, 7
-    const uint32_t hi_e = __builtin_amdgcn_perm(E2M1Bytes<T>::hi[0], E2M1Bytes<T>::hi[1], sel_e) | ((w << 4) & 0x80808080u);
-    const uint32_t hi_o = __builtin_amdgcn_perm(E2M1Bytes<T>::hi[0], E2M1Bytes<T>::hi[1], sel_o) | (w & 0x80808080u);
-    const uint32_t lo_e = __builtin_amdgcn_perm(E2M1Bytes<T>::lo[0], E2M1Bytes<T>::lo[1], sel_e);
-    const uint32_t lo_o = __builtin_amdgcn_perm(E2M1Bytes<T>::lo[0], E2M1Bytes<T>::lo[1], sel_o);
-    const uint32_t e01 = __builtin_amdgcn_perm(hi_e, lo_e, 0x05010400u), e23 = __builtin_amdgcn_perm(hi_e, lo_e, 0x07030602u);   // k 0, 2 | 4, 6
-    const uint32_t o01 = __builtin_amdgcn_perm(hi_o, lo_o, 0x05010400u), o23 = __builtin_amdgcn_perm(hi_o, lo_o, 0x07030602u);   // k 1, 3 | 5, 7
-    return v4i{(int)__builtin_amdgcn_perm(o01, e01, 0x05040100u), (int)__builtin_amdgcn_perm(o01, e01, 0x07060302u),
-               (int)__builtin_amdgcn_perm(o23, e23, 0x05040100u), (int)__builtin_amdgcn_perm(o23, e23, 0x07060302u)};
-}
-
-__device__ __forceinline__ v4f mfma16(v4i a, v4i b, bf16_t) {
-    typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-}
-__device__ __forceinline__ v4f mfma16(v4i a, v4i b, f16_t) {
-    typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-}
-
+// partial sum: 4 FMAs by the lane's scale 2^(s[n, block] - 127) add it to the accumulators.  (The decode, the MFMA and the scale:
+// mx_decode.h.)
 template <typename T>
 __global__ __launch_bounds__(64 * kMfmaWaves) void k_mx_decode_mfma(const T *__restrict__ x, const uint8_t *__restrict__ W,
                                                                      const uint8_t *__restrict__ Ws, int64_t M, int64_t N, int64_t K,
