@@ -14,13 +14,14 @@ allocation, dtype casts of activations/bias (reference: functional.py:764-766), 
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _mx_native, _native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moemlp_native, _mx_native, _native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -2053,3 +2054,150 @@ def matmul_mxfp4_experts(input: Tensor, weight: Tensor, weight_scales: Tensor, e
             _moe_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
                                  ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode, stream), what)
     return out
+
+
+# ============================================================================= the MXFP4 mixture-of-experts MLP
+# libmbnb_moemlp.so: the gate / up launch with the gated activation as its epilogue, the down launch into an f32
+# workspace and the routed sum over a token's slots, the two expert launches on a grid sized by the routing.  Ids and routing
+# weights are read on the device.
+def _moemlp_operands(what: str, input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor],
+                     per_slot: bool, dtype: Optional[torch.dtype], routing_weights: Optional[Tensor] = None):
+    """The checks of matmul_mxfp4_experts for one projection of the MLP -> (x, w, s, ids, b, rw, T, A, E, N, K, out dtype, its code)"""
+    grads = (input, bias, routing_weights)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in grads):
+        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its input, bias or routing weights "
+                                  "(call it under torch.no_grad(), or detach them)")
+    if weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8 or weight.dim() not in (3, 4) or weight_scales.dim() != 3:
+        raise ValueError(f"{what}: weight must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16] and weight_scales uint8 [E, N, K / 32]")
+    if weight.dim() == 4:
+        if weight.shape[3] != _moemlp_native.BLOCK // 2:
+            raise ValueError(f"{what}: a 4-D weight is the blocks layout [E, N, K / 32, 16], got {tuple(weight.shape)}")
+        weight = weight.reshape(weight.shape[0], weight.shape[1], -1)
+    E, N, K = weight.shape[0], weight.shape[1], weight.shape[2] * 2
+    _mx_width(K, what)
+    if E <= 0 or N <= 0:
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} has no expert or no output feature")
+    if E > _moemlp_native.MAX_EXPERTS:
+        raise ValueError(f"{what}: {E} experts exceed the {_moemlp_native.MAX_EXPERTS} of one launch")
+    if tuple(weight_scales.shape) != (E, N, K // _moemlp_native.BLOCK):
+        raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: "
+                         f"expected {(E, N, K // _moemlp_native.BLOCK)}")
+    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
+        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
+    T, A = expert_ids.shape
+    want = (T, A, K) if per_slot else (T, K)
+    if tuple(input.shape) != want:
+        raise ValueError(f"{what}: input {tuple(input.shape)} does not match expert_ids {tuple(expert_ids.shape)} and K = {K}: "
+                         f"expected {'[T, A, K]' if per_slot else '[T, K]'} = {want}")
+    if input.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{what}: input must be float16 or bfloat16 (16-bit activations), got {input.dtype}")
+    if bias is not None and tuple(bias.shape) != (E, N):
+        raise ValueError(f"{what}: bias {tuple(bias.shape)} does not match [E, N] = {(E, N)}")
+    if routing_weights is not None and (tuple(routing_weights.shape) != (T, A) or not routing_weights.dtype.is_floating_point):
+        raise ValueError(f"{what}: routing_weights must be a floating-point tensor [T, A] = {(T, A)}, got {routing_weights.dtype} "
+                         f"{tuple(routing_weights.shape)}")
+    if A > _moemlp_native.MAX_PAIRS:
+        raise ValueError(f"{what}: {A} slots per token exceed the {_moemlp_native.MAX_PAIRS} pairs of one launch")
+    out_dtype = input.dtype if dtype is None else dtype
+    ocode = dtype_code(out_dtype, what)
+    for t in (input, weight, expert_ids):
+        _check_device(t, what)
+    x = _aligned16(input)
+    w = _aligned16(weight)
+    s = weight_scales.to(x.device).contiguous()
+    ids = expert_ids.to(x.device)
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        ids = ids.to(torch.int32).contiguous()
+    b = None if bias is None else bias.to(x.device).contiguous()
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    rw = None if routing_weights is None else routing_weights.to(x.device)
+    if rw is not None and (rw.dtype not in _native.DTYPE_CODE or not rw.is_contiguous()):
+        rw = (rw if rw.dtype in _native.DTYPE_CODE else rw.float()).contiguous()
+    return x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode
+
+
+def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                             alpha: float = 1.702, limit: float = 7.0, dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    The gate / up projection of a mixture-of-experts MLP with the gated activation as its epilogue -> ``[T, A, I]``.  `weight` uint8
+    [E, 2I, K / 2] (or the blocks layout [E, 2I, K / 32, 16]) with the checkpoint's interleaved rows, row 2j gate j and row 2j + 1 up
+    j; `weight_scales` uint8 [E, 2I, K / 32]; `bias` [E, 2I] or None, interleaved the same way; `input` [T, K], f16 or bf16, shared
+    by a token's slots; `expert_ids` an integer tensor [T, A].  With ``pre = matmul_mxfp4_experts(..., dtype=float32)`` (the same bits),
+
+        g = min(pre[..., 2j], limit);  u = clamp(pre[..., 2j + 1], -limit, limit)
+        out[..., j] = (u + 1) * (g * (1 / (1 + exp(-alpha * g))))
+
+    in f32, one rounding to `dtype` (default: the input's).  One launch for up to 1024 pairs (more are cut over the tokens) on a
+    grid of ceil(2I / 16) x min(E, pairs) workgroups; the ids are read on the device, so nothing synchronises (an int32 contiguous
+    `expert_ids` is passed as the caller's own tensor).  A pair whose id is outside [0, E) (-1 pads) gets a row of +0.0.  At most
+    1024 experts.  `limit` may be ``inf``.  Inference only: no gradient is defined.
+    """
+    what = "matmul_mxfp4_experts_glu"
+    alpha, limit = float(alpha), float(limit)
+    if not math.isfinite(alpha) or not limit > 0:
+        raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
+    if weight.dim() in (3, 4) and weight.shape[1] % 2:
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _moemlp_operands(what, input, weight, weight_scales, expert_ids, bias, False, dtype)
+    I = N // 2
+    out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
+    if T * A == 0:
+        return out
+    step = max(1, _moemlp_native.MAX_PAIRS // A)             # tokens per launch
+    fn = _moemlp_native.lib().mbnb_moemlp_gate_up_glu
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for t0 in range(0, T, step):
+            t1 = min(T, t0 + step)
+            _moemlp_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, I, ptr(ids[t0:t1]), ptr(b),
+                                    0 if b is None else _native.DTYPE_CODE[b.dtype], alpha, limit, ptr(out[t0:t1]), ocode, stream), what)
+    return out
+
+
+def matmul_mxfp4_experts_sum(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
+                             bias: Optional[Tensor] = None, dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    The down projection of a mixture-of-experts MLP and the routed, weighted sum over a token's slots -> ``[T, N]``:
+    ``out[t] = sum_a routing_weights[t, a] * (input[t, a] @ W[expert_ids[t, a]]^T + bias[expert_ids[t, a]])``.  `input` [T, A, K],
+    f16 or bf16; `weight` uint8 [E, N, K / 2] (or the blocks layout), `weight_scales` uint8 [E, N, K / 32], `bias` [E, N] or None;
+    `routing_weights` [T, A], f32, f16 or bf16, read as f32.
+
+    Two launches for up to 1024 pairs (more are cut over the tokens): the projection in f32, with the bits of
+    ``matmul_mxfp4_experts(..., dtype=float32)``, into a workspace that is a ``torch.empty`` of this call, then one thread per output
+    runs ``acc = fmaf(rw[t, a], y[t, a, n], acc)`` over the slots in their order from +0.0 and rounds once to `dtype` (default: the
+    input's).  A slot whose id is outside [0, E) is skipped, its routing weight unread; a token without a slot in range gets +0.0.
+    Ids and routing weights are read on the device (contiguous tensors of a supported dtype are passed as the caller's own), so a
+    captured graph serves a new routing once both are overwritten in place.  At most 1024 experts.  Inference only.
+    """
+    what = "matmul_mxfp4_experts_sum"
+    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _moemlp_operands(what, input, weight, weight_scales, expert_ids, bias, True, dtype,
+                                                                           routing_weights)
+    if T * A == 0:
+        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
+    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
+    step = max(1, _moemlp_native.MAX_PAIRS // A)             # tokens per call
+    ws_bytes = _moemlp_native.workspace_bytes(min(T, step), A, N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    fn = _moemlp_native.lib().mbnb_moemlp_down_sum
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for t0 in range(0, T, step):
+            t1 = min(T, t0 + step)
+            _moemlp_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b),
+                                    0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(rw[t0:t1]), _native.DTYPE_CODE[rw.dtype],
+                                    ptr(out[t0:t1]), ocode, ptr(ws), ws_bytes, stream), what)
+    return out
+
+
+def moe_mlp_mxfp4(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor, gate_up_bias: Optional[Tensor], down_weight: Tensor,
+                  down_scales: Tensor, down_bias: Optional[Tensor], expert_ids: Tensor, routing_weights: Tensor, alpha: float = 1.702,
+                  limit: float = 7.0, dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    The expert MLP of a mixture-of-experts block (gpt-oss) for the tokens `input` [T, H] -> ``[T, H']``:
+    ``matmul_mxfp4_experts_sum(matmul_mxfp4_experts_glu(input, gate_up..., expert_ids, alpha, limit), down..., expert_ids,
+    routing_weights, dtype=dtype)`` and nothing more: three launches, the intermediate [T, A, I] in the input's dtype.  The router
+    (`expert_ids`, `routing_weights`) stays the caller's.
+    """
+    h = matmul_mxfp4_experts_glu(input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, alpha, limit)
+    return matmul_mxfp4_experts_sum(h, down_weight, down_scales, expert_ids, routing_weights, down_bias, dtype)
