@@ -26,9 +26,10 @@ from .functional import (
     sparse_coo_from_dense, quantize_sparse_coo, spmm_coo, spmm_coo_int8,
     quantize_mx, dequantize_mx, quantize_mxfp4, dequantize_mxfp4, matmul_mxfp4,
     matmul_mxfp4_experts, matmul_mxfp4_experts_glu, matmul_mxfp4_experts_sum, moe_mlp_mxfp4,
+    moe_router_topk, moe_block_mxfp4,
 )
 from .nn import (Linear4bit, Linear4bitGroup, Linear4bitLoRA, Linear4bitLoRAGroup, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
-                 OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup, LinearMXFP4, ExpertsMXFP4, MoEMLPMXFP4)
+                 OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup, LinearMXFP4, ExpertsMXFP4, MoEMLPMXFP4, MoERouterTopK, MoEBlockMXFP4)
 from .optim import (Adam8bit, AdamW8bit, Lion8bit, SGD8bit, PagedAdam, PagedAdamW, PagedLion,
                     quantize_state, dequantize_state)
 from .integration import (
@@ -70,4 +71,5 @@ __all__ = [
     'quantize_mx', 'dequantize_mx', 'quantize_mxfp4', 'dequantize_mxfp4', 'matmul_mxfp4', 'LinearMXFP4',
     'matmul_mxfp4_experts', 'ExpertsMXFP4',
     'matmul_mxfp4_experts_glu', 'matmul_mxfp4_experts_sum', 'moe_mlp_mxfp4', 'MoEMLPMXFP4',
+    'moe_router_topk', 'MoERouterTopK', 'moe_block_mxfp4', 'MoEBlockMXFP4',
 ]

@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moemlp_native, _mx_native, _native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moemlp_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -2201,3 +2201,84 @@ def moe_mlp_mxfp4(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor,
     """
     h = matmul_mxfp4_experts_glu(input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, alpha, limit)
     return matmul_mxfp4_experts_sum(h, down_weight, down_scales, expert_ids, routing_weights, down_bias, dtype)
+
+
+# ============================================================================= the router of the mixture-of-experts block
+# libmbnb_router.so: the router's logits in f32, the top-k selection (ties to the lower expert) and the softmax over
+# the selected logits in one launch; int32 ids and the routing weights, as the launches above read them.
+_ROUTER_WEIGHT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def moe_router_topk(input: Tensor, weight: Tensor, bias: Optional[Tensor] = None, top_k: int = 4,
+                    weights_dtype: torch.dtype = torch.float32, return_logits: bool = False):
+    """
+    The router of a mixture-of-experts block (gpt-oss): ``logits = input @ weight^T + bias`` in f32, the `top_k` largest per token
+    and the softmax over those -> ``(expert_ids int32 [T, top_k], routing_weights [T, top_k])``, plus ``logits`` f32 [T, E] with
+    ``return_logits=True``.  `input` [..., K], f16 or bf16, is flattened to [T, K]; `weight` [E, K] of the same dtype; `bias` [E] or
+    None, read as f32.
+
+    One launch of `k_router`, one workgroup per token.  The logits are accumulated in f32 from the exact products and are NOT
+    rounded to 16 bits, as ``F.linear`` would round them: fewer ties.  The ids are in descending order of the logit; among equal
+    logits (-0 equals +0) the lower expert index comes first, and a NaN logit ranks above everything, so the routing of a token
+    does not depend on the batch it is in: its ids, weights and logits are bit-equal alone and in any batch.  With the selected
+    logits v, ``w[a] = exp(v[a] - v[0]) / sum_a exp(v[a] - v[0])``, the sum in slot order, every operation in f32, one rounding
+    to `weights_dtype` (float32, float16 or bfloat16).  The outputs are ``torch.empty`` tensors of this call and nothing
+    synchronises, so the call can be captured in a graph.  At most 1024 experts, `top_k` at most ``min(E, 32)``, K a multiple of
+    8 up to 16384.  Inference only: no gradient is defined.
+    """
+    what = "moe_router_topk"
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, weight, bias)):
+        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its input, weight or bias "
+                                  "(call it under torch.no_grad(), or detach them)")
+    if weight.dim() != 2:
+        raise ValueError(f"{what}: weight must be [E, K], got {tuple(weight.shape)}")
+    E, K = weight.shape
+    if E <= 0 or E > _router_native.MAX_EXPERTS:
+        raise ValueError(f"{what}: {E} experts, 1 to {_router_native.MAX_EXPERTS} in one launch")
+    if K <= 0 or K % _router_native.CHUNK or K > _router_native.MAX_K:
+        raise ValueError(f"{what}: the last dimension ({K}) must be a positive multiple of {_router_native.CHUNK}, at most {_router_native.MAX_K}")
+    if input.dim() < 1 or input.shape[-1] != K:
+        raise ValueError(f"{what}: input {tuple(input.shape)} does not match weight {tuple(weight.shape)} (K = {K})")
+    if input.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{what}: input must be float16 or bfloat16 (16-bit activations), got {input.dtype}")
+    if weight.dtype != input.dtype:
+        raise ValueError(f"{what}: weight ({weight.dtype}) must have the input's dtype ({input.dtype})")
+    if bias is not None and (tuple(bias.shape) != (E,) or not bias.dtype.is_floating_point):
+        raise ValueError(f"{what}: bias must be a floating-point tensor [E] = {(E,)}, got {bias.dtype} {tuple(bias.shape)}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1 or top_k > min(E, _router_native.MAX_TOPK):
+        raise ValueError(f"{what}: top_k ({top_k!r}) must be an integer from 1 to min(E, {_router_native.MAX_TOPK}) = {min(E, _router_native.MAX_TOPK)}")
+    if weights_dtype not in _ROUTER_WEIGHT_DTYPES:
+        raise ValueError(f"{what}: weights_dtype must be float32, float16 or bfloat16, got {weights_dtype}")
+    for t in (input, weight):
+        _check_device(t, what)
+    x = _aligned16(input.reshape(-1, K))
+    w = _aligned16(weight.to(x.device))
+    b = None if bias is None else bias.to(x.device).contiguous()
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    T = x.shape[0]
+    ids = torch.empty(T, top_k, dtype=torch.int32, device=x.device)
+    rw = torch.empty(T, top_k, dtype=weights_dtype, device=x.device)
+    logits = torch.empty(T, E, dtype=torch.float32, device=x.device) if return_logits else None
+    if T > 0:
+        with on_device(x.device):
+            _router_native.check(_router_native.lib().mbnb_router_topk_softmax(
+                ptr(x), T, K, dtype_code(x.dtype, what), ptr(w), E, ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], top_k,
+                ptr(ids), ptr(rw), _native.DTYPE_CODE[weights_dtype], ptr(logits), stream_ptr(x.device)), what)
+    return (ids, rw, logits) if return_logits else (ids, rw)
+
+
+def moe_block_mxfp4(input: Tensor, router_weight: Tensor, router_bias: Optional[Tensor], gate_up_weight: Tensor, gate_up_scales: Tensor,
+                    gate_up_bias: Optional[Tensor], down_weight: Tensor, down_scales: Tensor, down_bias: Optional[Tensor], top_k: int = 4,
+                    alpha: float = 1.702, limit: float = 7.0, return_routing: bool = False):
+    """
+    The whole mixture-of-experts block (gpt-oss `mlp`) for `input` [..., H] -> ``[..., H]`` in the input's dtype:
+    ``moe_mlp_mxfp4(x, experts..., *moe_router_topk(x, router_weight, router_bias, top_k))`` and nothing more: four launches in
+    three C calls, no torch op, no synchronisation and no host-side tensor between the hidden state and its output.  With
+    ``return_routing=True`` also ``(expert_ids, routing_weights)``, [T, top_k] over the flattened tokens.
+    """
+    x = input.reshape(-1, input.shape[-1]) if input.dim() != 2 else input
+    ids, rw = moe_router_topk(x, router_weight, router_bias, top_k)
+    out = moe_mlp_mxfp4(x, gate_up_weight, gate_up_scales, gate_up_bias, down_weight, down_scales, down_bias, ids, rw, alpha, limit)
+    out = out.reshape(*input.shape[:-1], out.shape[-1])
+    return (out, (ids, rw)) if return_routing else out

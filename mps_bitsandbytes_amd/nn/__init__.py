@@ -10,7 +10,9 @@ matmul_4bit_lora_grouped (libmbnb_lora.so), Linear4bitMultiLoRA / Linear4bitMult
 matmul_4bit_multilora_grouped (libmbnb_mlora.so), LinearMXFP4 (an OCP MXFP4 weight on the block-scaled MFMA) -> matmul_mxfp4
 (libmbnb_mx.so), ExpertsMXFP4 (the MXFP4 expert weights of a mixture-of-experts projection, the expert of every (token, slot) pair
 read on the device) -> matmul_mxfp4_experts (libmbnb_moe.so), MoEMLPMXFP4 (the gate / up and down expert weights of a gpt-oss MLP under
-the checkpoint's names) -> moe_mlp_mxfp4 (libmbnb_moemlp.so).  `_base.py` holds what they share.
+the checkpoint's names) -> moe_mlp_mxfp4 (libmbnb_moemlp.so), MoERouterTopK (the router of that block: logits, top-k and softmax in one
+launch) -> moe_router_topk (libmbnb_router.so), MoEBlockMXFP4 (the router and the expert MLP under the checkpoint's `mlp.*` names) ->
+moe_block_mxfp4.  `_base.py` holds what they share.
 """
 from .embedding import Embedding4bit, Embedding8bit, EmbeddingFP4, EmbeddingNF4
 from .linear4bit import Linear4bit, Params4bit
@@ -22,9 +24,10 @@ from .linear_fp8 import LinearFP8
 from .linear_mxfp4 import LinearMXFP4
 from .experts_mxfp4 import ExpertsMXFP4
 from .moe_mlp_mxfp4 import MoEMLPMXFP4
+from .moe_block_mxfp4 import MoEBlockMXFP4, MoERouterTopK
 from .outlier_aware import OutlierAwareLinear
 from .switchback import SwitchBackLinear, SwitchBackLinearCallback
 
-__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'LinearMXFP4', 'ExpertsMXFP4', 'MoEMLPMXFP4', 'OutlierAwareLinear',
+__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'LinearMXFP4', 'ExpertsMXFP4', 'MoEMLPMXFP4', 'MoERouterTopK', 'MoEBlockMXFP4', 'OutlierAwareLinear',
                   'Embedding4bit', 'Embedding8bit', 'EmbeddingNF4', 'EmbeddingFP4',
                   'SwitchBackLinear', 'SwitchBackLinearCallback'])
