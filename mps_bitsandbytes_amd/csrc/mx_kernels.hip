@@ -21,7 +21,7 @@ namespace {
 using mbnb::bf16_t;
 using mbnb::f16_t;
 using mbnb::fail;
-// the scale, the byte-table decode, the MFMA of one block, the bias load and the output store: mx_decode.h, shared with moe_kernels.hip
+// the scale, the bias load, the output store and the 16 x 16 MFMA decode tile: mx_decode.h, shared with the two expert libraries
 using mbnb::mx::v4i;
 using mbnb::mx::v4f;
 using mbnb::mx::kNaNScale;
@@ -30,8 +30,10 @@ using mbnb::mx::kMfmaWaves;
 using mbnb::mx::scale_value;
 using mbnb::mx::load_bias;
 using mbnb::mx::store_out;
-using mbnb::mx::decode8_16;
-using mbnb::mx::mfma16;
+using mbnb::mx::TileLds;
+using mbnb::mx::TileSums;
+using mbnb::mx::tile_walk;
+using mbnb::mx::tile_reduce;
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 
@@ -478,99 +480,38 @@ __global__ __launch_bounds__(kThreads) void k_mx_decode(const T *__restrict__ x,
 }
 
 // k_mx_decode_mfma: 2 to 16 rows of 16-bit activations on v_mfma_f32_16x16x32_{bf16,f16}, whose K = 32 is one MX block.  A workgroup
-// of 8 waves owns 16 weight rows and ALL of K: wave w takes the k-steps w, w + 8, ... of 4 blocks (128 k) each, and the eight
-// accumulators are added through LDS at the end, in wave order; the loads of two k-steps are requested before the first is used.
-// (Two tiles of 16 weight rows per workgroup, every x fragment feeding two MFMAs, measured slower at 11008 rows: DESIGN.md §27.)
-// Per k-step lane (n = l & 15, g = l >> 4) fetches the 16 bytes of
-// block 4 c + g of weight row n (a wave reads 64 consecutive bytes of each of its 16 rows) and a 4 x 4 transpose across the four
-// lane groups (two v_permlane32_swap, two v_permlane16_swap) leaves in register q the dword g of block 4 c + q: the B fragment
-// B[k = 8 g + j][column n] of the MFMA of block q.  Its 8 codes become 16-bit values by byte lookups (v_perm_b32 over the 8
-// magnitudes' high and low bytes, the sign OR-ed into the high byte).  The A fragment A[row m = l & 15][k = 8 g + j] is 16 bytes of x
-// straight from memory (rows past M and k past K as zeros, never read).  D (column n on the lane, rows 4 g + r) is the block's
-// partial sum: 4 FMAs by the lane's scale 2^(s[n, block] - 127) add it to the accumulators.  (The decode, the MFMA and the scale:
-// mx_decode.h.)
+// of 8 waves owns 16 weight rows and ALL of K against 16 activation rows: the decode tile of mx_decode.h.  tile_walk gives every
+// wave its partial sums over the k-steps w, w + 8, ... of 4 blocks (128 k) each, tile_reduce adds the eight through LDS in wave
+// order; the expert kernels (moe_kernels.hip, moemlp_kernels.hip) call the same two functions, so their bits are this kernel's.
+// What is this kernel's own: where a workgroup finds its rows and columns, and the store.  The A fragment A[row m = l & 15]
+// [k = 8 g + j] is 16 bytes of x straight from memory (rows past M and k past K count as zeros); D is column n = l & 15 on the lane,
+// rows 4 g + r.  (Two tiles of 16 weight rows per workgroup, every x fragment feeding two MFMAs, measured slower at 11008 rows:
+// DESIGN.md §27.)
 template <typename T>
 __global__ __launch_bounds__(64 * kMfmaWaves) void k_mx_decode_mfma(const T *__restrict__ x, const uint8_t *__restrict__ W,
                                                                      const uint8_t *__restrict__ Ws, int64_t M, int64_t N, int64_t K,
                                                                      const void *__restrict__ bias, int bias_dtype, void *__restrict__ out,
                                                                      int out_dtype, int row_chunks) {
-    static_assert(sizeof(T) == 2, "16-bit activations");
-    constexpr int U = 2;                                     // k-steps whose loads are requested before the first of them is used
-    __shared__ float red[kMfmaWaves][4][64];
-    __shared__ int red_ff[kMfmaWaves][64];
+    __shared__ TileLds lds;
     const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t m0 = (int64_t)(blockIdx.x % row_chunks) * MBNB_MX_DECODE_ROWS;
     const int64_t n0 = (int64_t)(blockIdx.x / row_chunks) * 16;
-    const int64_t KB = K / 32, ldw = K / 2, last = KB - 1;
+    const int64_t KB = K / 32, ldw = K / 2;
     const int64_t n = n0 + fr < N ? n0 + fr : N - 1;         // a column past N reads the last weight row and stores nothing
-    const uint8_t *w_row = W + n * ldw, *s_row = Ws + n * KB;
-    const bool x_live = m0 + fr < M;
+    const bool x_live = m0 + fr < M;                         // a row past M reads row 0 and counts as zeros
     const T *x_row = x + (x_live ? m0 + fr : 0) * K + 8 * g;
 
-    v4f acc = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    bool ff = false;
-    const int64_t steps = (KB + 3) / 4;
-    for (int64_t c0 = wave; c0 < steps; c0 += kMfmaWaves * U) {
-        // every load is unconditional, from a clamped (valid) address; what lies past K or M becomes zeros in registers
-        v4i wq[U], xa[U][4];
-        uint32_t sb[U][4];
+    const TileSums part = tile_walk<T>(x_row, x_live, W + n * ldw, Ws + n * KB, KB, wave, g);
+    const bool stores = wave == 0 && n0 + fr < N;
+    const float b = stores && bias ? load_bias(bias, bias_dtype, n) : 0.0f;   // requested before the reduction's barrier
+    v4f s;
+    const bool col_nan = tile_reduce(lds, part, wave, lane, s);
+    if (stores) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t c = c0 + u * kMfmaWaves, blk = 4 * c + g;
-            wq[u] = __builtin_nontemporal_load((const v4i *)(w_row + (blk < KB ? blk : last) * 16));
-            if (blk >= KB) wq[u] = v4i{0, 0, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool in = 4 * c + q < KB;
-                const int64_t b = in ? 4 * c + q : last;
-                sb[u][q] = s_row[b];
-                if (!in) sb[u][q] = (uint32_t)kOneScale;
-                xa[u][q] = *(const v4i *)(x_row + b * 32);
-                if (!(in && x_live)) xa[u][q] = v4i{0, 0, 0, 0};
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (c0 + u * kMfmaWaves >= steps) break;         // wave-uniform
-            // register q of lane group g holds dword q of block g; after the transpose, dword g of block q
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            const v2u s02 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][0], (unsigned)wq[u][2], false, false);
-            const v2u s13 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][1], (unsigned)wq[u][3], false, false);
-            const v2u t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-            const v2u t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-            const uint32_t wb[4] = {t01[0], t01[1], t23[0], t23[1]};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4f d = mfma16(xa[u][q], decode8_16<T>(wb[q]), T{});
-                const uint32_t byte = sb[u][q];
-                ff |= byte == (uint32_t)kNaNScale;
-                const float sv = scale_value(byte == (uint32_t)kNaNScale ? (uint32_t)kOneScale : byte);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(d[r], sv, acc[r]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][r][lane] = acc[r];
-    red_ff[wave][lane] = ff;
-    __syncthreads();
-    if (wave == 0) {                                         // the eight partial sums, in wave order
-        bool col_nan = false;
-        v4f s = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int w = 0; w < kMfmaWaves; ++w) {
-            col_nan |= red_ff[w][lane] != 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[r] += red[w][r][lane];
-        }
-        if (n0 + fr < N) {
-            const float b = bias ? load_bias(bias, bias_dtype, n) : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t m = m0 + 4 * g + r;
-                if (m < M) store_out(out, out_dtype, m * N + n, col_nan ? __uint_as_float(0x7FC00000u) : s[r] + b);
-            }
+        for (int r = 0; r < 4; ++r) {
+            const int64_t m = m0 + 4 * g + r;
+            if (m < M) store_out(out, out_dtype, m * N + n, col_nan ? __uint_as_float(0x7FC00000u) : s[r] + b);
         }
     }
 }

@@ -1980,111 +1980,40 @@ def matmul_mxfp4(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Opt
 # ============================================================================= MXFP4 expert linears (mixture of experts)
 # The tensors MXFP4 checkpoints ship are expert weights: [E, N, K / 32, 16] blocks plus [E, N, K / 32] scale bytes, and a router
 # picks `top_k` of the E experts per token.  One launch of libmbnb_moe.so serves a projection of every (token, slot) pair, the
-# expert ids read on the device.
-def matmul_mxfp4_experts(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
-                         dtype: Optional[torch.dtype] = None) -> Tensor:
-    """
-    ``out[t, a] = input_row(t, a) @ W[expert_ids[t, a]]^T + bias[expert_ids[t, a]]`` -> ``[T, A, N]``, over E MXFP4 weights:
-    `weight` uint8 [E, N, K / 2] (or the checkpoint's blocks layout [E, N, K / 32, 16], the same bytes), `weight_scales` uint8
-    [E, N, K / 32], `bias` [E, N] or None, `expert_ids` an integer tensor [T, A].  `input` is [T, K] (every slot of a token shares
-    its row: a gate / up projection) or [T, A, K] (a row per slot: a down projection), f16 or bf16, not quantised.
-
-    One launch of `k_mx_experts` for up to 1024 pairs (more are cut over the tokens into several launches): the ids are read on
-    the device, so nothing synchronises and a captured graph serves a new routing once `expert_ids` is overwritten in place (an
-    int32 contiguous `expert_ids` is passed as the caller's own tensor; other integer dtypes are converted).  f32 accumulation,
-    the scale applied per block, the bias added in f32, one rounding to `dtype` (default: the input's); a pair's bits are those
-    of ``matmul_mxfp4(row, W[e], s[e], bias[e], act_format="none")`` on 2 to 16 rows, whatever else is in the call.  A pair whose
-    id is outside [0, E) (-1 pads) gets a row of +0.0.  Inference only: no gradient is defined.  The routed sum over the slots and
-    the activation between two projections stay torch ops of the caller.
-    """
-    what = "matmul_mxfp4_experts"
-    if torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)):
-        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its input or bias "
-                                  "(call it under torch.no_grad(), or detach them)")
-    if weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8 or weight.dim() not in (3, 4) or weight_scales.dim() != 3:
-        raise ValueError(f"{what}: weight must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16] and weight_scales uint8 [E, N, K / 32]")
-    if weight.dim() == 4:
-        if weight.shape[3] != _moe_native.BLOCK // 2:
-            raise ValueError(f"{what}: a 4-D weight is the blocks layout [E, N, K / 32, 16], got {tuple(weight.shape)}")
-        weight = weight.reshape(weight.shape[0], weight.shape[1], -1)
-    E, N, K = weight.shape[0], weight.shape[1], weight.shape[2] * 2
-    _mx_width(K, what)
-    if E <= 0 or N <= 0:
-        raise ValueError(f"{what}: weight {tuple(weight.shape)} has no expert or no output feature")
-    if tuple(weight_scales.shape) != (E, N, K // _moe_native.BLOCK):
-        raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: "
-                         f"expected {(E, N, K // _moe_native.BLOCK)}")
-    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
-        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
-    T, A = expert_ids.shape
-    if input.dim() not in (2, 3):
-        raise ValueError(f"{what}: input must be [T, K] (shared by a token's slots) or [T, A, K] (a row per slot), got {tuple(input.shape)}")
-    per_slot = input.dim() == 3
-    if tuple(input.shape) != ((T, A, K) if per_slot else (T, K)):
-        raise ValueError(f"{what}: input {tuple(input.shape)} does not match expert_ids {tuple(expert_ids.shape)} and K = {K}: "
-                         f"expected {(T, A, K) if per_slot else (T, K)}")
-    if input.dtype not in (torch.float16, torch.bfloat16):
-        raise ValueError(f"{what}: input must be float16 or bfloat16 (16-bit activations), got {input.dtype}")
-    if bias is not None and tuple(bias.shape) != (E, N):
-        raise ValueError(f"{what}: bias {tuple(bias.shape)} does not match [E, N] = {(E, N)}")
-    if A > _moe_native.MAX_PAIRS:
-        raise ValueError(f"{what}: {A} slots per token exceed the {_moe_native.MAX_PAIRS} pairs of one launch")
-    out_dtype = input.dtype if dtype is None else dtype
-    ocode = dtype_code(out_dtype, what)
-    for t in (input, weight, expert_ids):
-        _check_device(t, what)
-    x = _aligned16(input)
-    w = _aligned16(weight)
-    s = weight_scales.to(x.device).contiguous()
-    ids = expert_ids.to(x.device)
-    if ids.dtype != torch.int32 or not ids.is_contiguous():
-        ids = ids.to(torch.int32).contiguous()
-    b = None if bias is None else bias.to(x.device).contiguous()
-    if b is not None and b.dtype not in _native.DTYPE_CODE:
-        b = b.float()
-    out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
-    if T * A == 0:
-        return out
-    step = max(1, _moe_native.MAX_PAIRS // A)                # tokens per launch
-    fn = _moe_native.lib().mbnb_moe_mxfp4_experts
-    with on_device(x.device):
-        stream = stream_ptr(x.device)
-        for t0 in range(0, T, step):
-            t1 = min(T, t0 + step)
-            _moe_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
-                                 ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode, stream), what)
-    return out
-
-
-# ============================================================================= the MXFP4 mixture-of-experts MLP
-# libmbnb_moemlp.so (DESIGN.md §29): the gate / up launch with the gated activation as its epilogue, the down launch into an f32
-# workspace and the routed sum over a token's slots, the two expert launches on a grid sized by the routing.  Ids and routing
-# weights are read on the device.
-def _moemlp_operands(what: str, input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor],
-                     per_slot: bool, dtype: Optional[torch.dtype], routing_weights: Optional[Tensor] = None):
-    """The checks of matmul_mxfp4_experts for one projection of the MLP -> (x, w, s, ids, b, rw, T, A, E, N, K, out dtype, its code)"""
+# expert ids read on the device.  _expert_operands is the one check and preparation of an expert projection's
+# operands, for this call and for the two of the MLP below.
+def _expert_operands(what: str, native, input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor],
+                     per_slot: Optional[bool], dtype: Optional[torch.dtype], routing_weights: Optional[Tensor] = None):
+    """The checks and the operand preparation of one expert projection -> (x, w, s, ids, b, rw, T, A, E, N, K, out dtype, its code).
+    `native` is the binding whose library serves the call: its BLOCK and MAX_PAIRS hold, and its MAX_EXPERTS where it has one.
+    `per_slot`: the input is [T, A, K] (True), [T, K] (False), or either (None)."""
     grads = (input, bias, routing_weights)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in grads):
-        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its input, bias or routing weights "
+        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its "
+                                  f"{'input or bias' if routing_weights is None else 'input, bias or routing weights'} "
                                   "(call it under torch.no_grad(), or detach them)")
     if weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8 or weight.dim() not in (3, 4) or weight_scales.dim() != 3:
         raise ValueError(f"{what}: weight must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16] and weight_scales uint8 [E, N, K / 32]")
     if weight.dim() == 4:
-        if weight.shape[3] != _moemlp_native.BLOCK // 2:
+        if weight.shape[3] != native.BLOCK // 2:
             raise ValueError(f"{what}: a 4-D weight is the blocks layout [E, N, K / 32, 16], got {tuple(weight.shape)}")
         weight = weight.reshape(weight.shape[0], weight.shape[1], -1)
     E, N, K = weight.shape[0], weight.shape[1], weight.shape[2] * 2
     _mx_width(K, what)
     if E <= 0 or N <= 0:
         raise ValueError(f"{what}: weight {tuple(weight.shape)} has no expert or no output feature")
-    if E > _moemlp_native.MAX_EXPERTS:
-        raise ValueError(f"{what}: {E} experts exceed the {_moemlp_native.MAX_EXPERTS} of one launch")
-    if tuple(weight_scales.shape) != (E, N, K // _moemlp_native.BLOCK):
+    if E > getattr(native, "MAX_EXPERTS", E):
+        raise ValueError(f"{what}: {E} experts exceed the {native.MAX_EXPERTS} of one launch")
+    if tuple(weight_scales.shape) != (E, N, K // native.BLOCK):
         raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: "
-                         f"expected {(E, N, K // _moemlp_native.BLOCK)}")
+                         f"expected {(E, N, K // native.BLOCK)}")
     if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
         raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
     T, A = expert_ids.shape
+    if per_slot is None:
+        if input.dim() not in (2, 3):
+            raise ValueError(f"{what}: input must be [T, K] (shared by a token's slots) or [T, A, K] (a row per slot), got {tuple(input.shape)}")
+        per_slot = input.dim() == 3
     want = (T, A, K) if per_slot else (T, K)
     if tuple(input.shape) != want:
         raise ValueError(f"{what}: input {tuple(input.shape)} does not match expert_ids {tuple(expert_ids.shape)} and K = {K}: "
@@ -2096,8 +2025,8 @@ def _moemlp_operands(what: str, input: Tensor, weight: Tensor, weight_scales: Te
     if routing_weights is not None and (tuple(routing_weights.shape) != (T, A) or not routing_weights.dtype.is_floating_point):
         raise ValueError(f"{what}: routing_weights must be a floating-point tensor [T, A] = {(T, A)}, got {routing_weights.dtype} "
                          f"{tuple(routing_weights.shape)}")
-    if A > _moemlp_native.MAX_PAIRS:
-        raise ValueError(f"{what}: {A} slots per token exceed the {_moemlp_native.MAX_PAIRS} pairs of one launch")
+    if A > native.MAX_PAIRS:
+        raise ValueError(f"{what}: {A} slots per token exceed the {native.MAX_PAIRS} pairs of one launch")
     out_dtype = input.dtype if dtype is None else dtype
     ocode = dtype_code(out_dtype, what)
     for t in (input, weight, expert_ids):
@@ -2117,6 +2046,44 @@ def _moemlp_operands(what: str, input: Tensor, weight: Tensor, weight_scales: Te
     return x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode
 
 
+def matmul_mxfp4_experts(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                         dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    ``out[t, a] = input_row(t, a) @ W[expert_ids[t, a]]^T + bias[expert_ids[t, a]]`` -> ``[T, A, N]``, over E MXFP4 weights:
+    `weight` uint8 [E, N, K / 2] (or the checkpoint's blocks layout [E, N, K / 32, 16], the same bytes), `weight_scales` uint8
+    [E, N, K / 32], `bias` [E, N] or None, `expert_ids` an integer tensor [T, A].  `input` is [T, K] (every slot of a token shares
+    its row: a gate / up projection) or [T, A, K] (a row per slot: a down projection), f16 or bf16, not quantised.
+
+    One launch of `k_mx_experts` for up to 1024 pairs (more are cut over the tokens into several launches): the ids are read on
+    the device, so nothing synchronises and a captured graph serves a new routing once `expert_ids` is overwritten in place (an
+    int32 contiguous `expert_ids` is passed as the caller's own tensor; other integer dtypes are converted).  f32 accumulation,
+    the scale applied per block, the bias added in f32, one rounding to `dtype` (default: the input's); a pair's bits are those
+    of ``matmul_mxfp4(row, W[e], s[e], bias[e], act_format="none")`` on 2 to 16 rows, whatever else is in the call.  A pair whose
+    id is outside [0, E) (-1 pads) gets a row of +0.0.  Inference only: no gradient is defined.  The routed sum over the slots and
+    the activation between two projections stay torch ops of the caller.
+    """
+    what = "matmul_mxfp4_experts"
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moe_native, input, weight, weight_scales, expert_ids, bias, None,
+                                                                          dtype)
+    per_slot = x.dim() == 3
+    out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
+    if T * A == 0:
+        return out
+    step = max(1, _moe_native.MAX_PAIRS // A)                # tokens per launch
+    fn = _moe_native.lib().mbnb_moe_mxfp4_experts
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for t0 in range(0, T, step):
+            t1 = min(T, t0 + step)
+            _moe_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
+                                 ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode, stream), what)
+    return out
+
+
+# ============================================================================= the MXFP4 mixture-of-experts MLP
+# libmbnb_moemlp.so (DESIGN.md §29): the gate / up launch with the gated activation as its epilogue, the down launch into an f32
+# workspace and the routed sum over a token's slots, the two expert launches on a grid sized by the routing.  Ids and routing
+# weights are read on the device.
 def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
                              alpha: float = 1.702, limit: float = 7.0, dtype: Optional[torch.dtype] = None) -> Tensor:
     """
@@ -2139,7 +2106,7 @@ def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tenso
         raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
     if weight.dim() in (3, 4) and weight.shape[1] % 2:
         raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
-    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _moemlp_operands(what, input, weight, weight_scales, expert_ids, bias, False, dtype)
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, False, dtype)
     I = N // 2
     out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
     if T * A == 0:
@@ -2171,7 +2138,7 @@ def matmul_mxfp4_experts_sum(input: Tensor, weight: Tensor, weight_scales: Tenso
     captured graph serves a new routing once both are overwritten in place.  At most 1024 experts.  Inference only.
     """
     what = "matmul_mxfp4_experts_sum"
-    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _moemlp_operands(what, input, weight, weight_scales, expert_ids, bias, True, dtype,
+    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, True, dtype,
                                                                            routing_weights)
     if T * A == 0:
         return torch.zeros(T, N, dtype=out_dtype, device=x.device)

@@ -80,6 +80,23 @@ def test_the_makefile_the_build_and_the_sources():
         assert definition.search(shared), name
         assert not definition.search(mx_src) and not definition.search(src), name
     assert "struct E2M1Bytes" in shared and "struct E2M1Bytes" not in mx_src and "struct E2M1Bytes" not in src
+    # the decode tile, the pair list and the checks of an expert call are ONE text: defined in the header, called by the kernel files
+    mlp_src = open(os.path.join(CSRC, "moemlp_kernels.hip")).read()
+    kernels = {"mx_kernels.hip": mx_src, "moe_kernels.hip": src, "moemlp_kernels.hip": mlp_src}
+    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers"):
+        definition = re.compile(r"^(?:__device__ __forceinline__|static) [\w ]+ " + name + r"\(", flags=re.M)
+        assert len(definition.findall(shared)) == 1, name
+        assert not any(definition.search(text) for text in kernels.values()), name
+    for name, text in kernels.items():
+        for inner in ("__builtin_amdgcn_permlane32_swap", "mfma16(", "decode8_16<"):
+            assert inner in shared and inner not in text, (name, inner)
+    calls = lambda text, name: len(re.findall(r"\b" + name + r"(?:<\w+>)?\(", text))     # whatever the arguments are called
+    for name in ("tile_walk", "tile_reduce"):
+        assert all(calls(text, name) == 1 for text in kernels.values()), name
+    assert calls(src, "list_pairs") == 1 == calls(mlp_src, "list_pairs") and calls(mx_src, "list_pairs") == 0
+    # the ballot over the ids occurs once; the only other ballots of the three files walk moemlp's presence bytes
+    assert shared.count("__ballot(") == 2 and "__ballot(" not in src and mlp_src.count("__ballot(") == 2 and "present[" in mlp_src
+    assert calls(src, "check_expert_call") == 1 == calls(src, "check_expert_pointers") and calls(mx_src, "check_expert_call") == 0
 
 
 def test_argument_errors_are_a_status_before_any_device_access():

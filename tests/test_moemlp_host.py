@@ -82,6 +82,19 @@ def test_the_makefile_the_build_and_the_source():
     for name in ("decode8_16", "mfma16", "scale_value", "load_bias", "store_out"):       # defined once, in the header the three files share
         assert re.search(r"__device__ __forceinline__ [\w ]+ " + name + r"\(", shared), name
         assert not re.search(r"__device__ __forceinline__ [\w ]+ " + name + r"\(", src), name
+    # the decode tile, the pair list and the checks of an expert call are the header's too: this file only calls them
+    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers"):
+        definition = re.compile(r"^(?:__device__ __forceinline__|static) [\w ]+ " + name + r"\(", flags=re.M)
+        assert len(definition.findall(shared)) == 1 and not definition.search(src), name
+    for inner in ("__builtin_amdgcn_permlane32_swap", "mfma16(", "decode8_16<"):
+        assert inner in shared and inner not in src, inner
+    calls = lambda name: len(re.findall(r"\b" + name + r"(?:<\w+>)?\(", src))            # whatever the arguments are called
+    assert calls("tile_walk") == 1 == calls("tile_reduce") == calls("list_pairs")
+    assert src.count("__ballot(") == 2 == shared.count("__ballot(")      # here the presence walk; the ballots over the ids are list_pairs'
+    # both entry points go through the shared shape check and the shared NULL and alignment checks
+    assert calls("check_expert_call") == 2 and calls("check_expert_pointers") + calls("check_expert_nulls") == 2 == 1 + calls("check_expert_alignment")
+    assert "MBNB_MOEMLP_MAX_PAIRS == mbnb::mx::kMaxPairs" in src and "MBNB_MOEMLP_ERR_ARG == mbnb::mx::kErrArg" in src
+    assert "MBNB_MOE_MAX_PAIRS == mbnb::mx::kMaxPairs" in open(os.path.join(CSRC, "moe_kernels.hip")).read()
 
 
 def test_argument_errors_are_a_status_before_any_device_access():

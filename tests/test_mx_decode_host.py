@@ -72,6 +72,15 @@ def test_the_source_keeps_to_host_h_and_last_launch():
     assert "set_kernel_name" not in src and "set_kernel_variant" not in src and '"mx_decode %s MT%d"' in src and "k_mx_decode_mfma" in src
     makefile = open(os.path.join(ROOT, "mps_bitsandbytes_amd", "csrc", "Makefile")).read()
     assert re.search(r"^mx_SRCS\s*:=\s*mx_kernels\.hip$", makefile, flags=re.M)
+    # the MFMA form's K walk and reduction are mx_decode.h's, the text the expert kernels call too: defined there once, called here once
+    shared = open(os.path.join(ROOT, "mps_bitsandbytes_amd", "csrc", "mx_decode.h")).read()
+    assert '#include "mx_decode.h"' in src
+    for name in ("tile_walk", "tile_reduce"):
+        definition = re.compile(r"^__device__ __forceinline__ [\w ]+ " + name + r"\(", flags=re.M)
+        assert len(definition.findall(shared)) == 1 and not definition.search(src), name
+    assert len(re.findall(r"\btile_walk<\w+>\(", src)) == 1 == len(re.findall(r"\btile_reduce\(", src))
+    for inner in ("__builtin_amdgcn_permlane32_swap", "mfma16(", "decode8_16<"):
+        assert inner in shared and inner not in src, inner
 
 
 # ----------------------------------------------------------------------------- the Python surface
