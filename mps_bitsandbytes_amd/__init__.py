@@ -27,6 +27,7 @@ from .functional import (
     quantize_mx, dequantize_mx, quantize_mxfp4, dequantize_mxfp4, matmul_mxfp4,
     matmul_mxfp4_experts, matmul_mxfp4_experts_glu, matmul_mxfp4_experts_sum, moe_mlp_mxfp4,
     moe_router_topk, moe_block_mxfp4,
+    matmul_mxfp4_experts_grouped, matmul_mxfp4_experts_grouped_glu, matmul_mxfp4_experts_grouped_sum, moe_grouped_plan,
 )
 from .nn import (Linear4bit, Linear4bitGroup, Linear4bitLoRA, Linear4bitLoRAGroup, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
                  OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup, LinearMXFP4, ExpertsMXFP4, MoEMLPMXFP4, MoERouterTopK, MoEBlockMXFP4)
@@ -72,4 +73,5 @@ __all__ = [
     'matmul_mxfp4_experts', 'ExpertsMXFP4',
     'matmul_mxfp4_experts_glu', 'matmul_mxfp4_experts_sum', 'moe_mlp_mxfp4', 'MoEMLPMXFP4',
     'moe_router_topk', 'MoERouterTopK', 'moe_block_mxfp4', 'MoEBlockMXFP4',
+    'matmul_mxfp4_experts_grouped', 'matmul_mxfp4_experts_grouped_glu', 'matmul_mxfp4_experts_grouped_sum', 'moe_grouped_plan',
 ]

@@ -1,6 +1,6 @@
 """
-The one load path of the thirteen native libraries.  A binding module (_native, _optim_native, _train_native, _sparse_native,
-_paged_native, _group_native, _lora_native, _batch_native, _mlora_native, _mx_native, _moe_native, _moemlp_native, _router_native) keeps what is its own -- LIB_PATH, ABI_VERSION, _PREFIX (of its `*_abi_version` / `*_last_error` exports), _CHECK_PREFIX (of check()'s
+The one load path of the fourteen native libraries.  A binding module (_native, _optim_native, _train_native, _sparse_native,
+_paged_native, _group_native, _lora_native, _batch_native, _mlora_native, _mx_native, _moe_native, _moemlp_native, _router_native, _moegemm_native) keeps what is its own -- LIB_PATH, ABI_VERSION, _PREFIX (of its `*_abi_version` / `*_last_error` exports), _CHECK_PREFIX (of check()'s
 message), _SIGNATURES, optionally _REQUIRES (binding modules whose library is loaded first), and the cache `_lib` / `_load_error` -- and a three-line `lib()`
 that returns the cached handle itself, so a call on the hot path never comes here.  Everything else works on that module's globals,
 read at the time of the call: assigning LIB_PATH (or clearing the cache) on the module redirects the next load.  The grouped decode

@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moemlp_native, _mx_native, _native, _router_native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -2060,12 +2060,15 @@ def matmul_mxfp4_experts(input: Tensor, weight: Tensor, weight_scales: Tensor, e
     the scale applied per block, the bias added in f32, one rounding to `dtype` (default: the input's); a pair's bits are those
     of ``matmul_mxfp4(row, W[e], s[e], bias[e], act_format="none")`` on 2 to 16 rows, whatever else is in the call.  A pair whose
     id is outside [0, E) (-1 pads) gets a row of +0.0.  Inference only: no gradient is defined.  The routed sum over the slots and
-    the activation between two projections stay torch ops of the caller.
+    the activation between two projections stay torch ops of the caller.  From `MOE_GROUPED_MIN_PAIRS` pairs up the call takes the
+    grouped GEMM of `matmul_mxfp4_experts_grouped`: the same bits, another `last_launch()`.
     """
     what = "matmul_mxfp4_experts"
     x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moe_native, input, weight, weight_scales, expert_ids, bias, None,
                                                                           dtype)
     per_slot = x.dim() == 3
+    if _takes_grouped(T * A, E):
+        return _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, None)
     out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
     if T * A == 0:
         return out
@@ -2098,7 +2101,8 @@ def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tenso
     in f32, one rounding to `dtype` (default: the input's).  One launch for up to 1024 pairs (more are cut over the tokens) on a
     grid of ceil(2I / 16) x min(E, pairs) workgroups; the ids are read on the device, so nothing synchronises (an int32 contiguous
     `expert_ids` is passed as the caller's own tensor).  A pair whose id is outside [0, E) (-1 pads) gets a row of +0.0.  At most
-    1024 experts.  `limit` may be ``inf``.  Inference only: no gradient is defined.
+    1024 experts.  `limit` may be ``inf``.  Inference only: no gradient is defined.  From `MOE_GROUPED_MIN_PAIRS` pairs up the call
+    takes the grouped GEMM of `matmul_mxfp4_experts_grouped_glu`: the same bits, another `last_launch()`.
     """
     what = "matmul_mxfp4_experts_glu"
     alpha, limit = float(alpha), float(limit)
@@ -2108,6 +2112,8 @@ def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tenso
         raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
     x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, False, dtype)
     I = N // 2
+    if _takes_grouped(T * A, E):
+        return _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, None)
     out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
     if T * A == 0:
         return out
@@ -2135,13 +2141,16 @@ def matmul_mxfp4_experts_sum(input: Tensor, weight: Tensor, weight_scales: Tenso
     runs ``acc = fmaf(rw[t, a], y[t, a, n], acc)`` over the slots in their order from +0.0 and rounds once to `dtype` (default: the
     input's).  A slot whose id is outside [0, E) is skipped, its routing weight unread; a token without a slot in range gets +0.0.
     Ids and routing weights are read on the device (contiguous tensors of a supported dtype are passed as the caller's own), so a
-    captured graph serves a new routing once both are overwritten in place.  At most 1024 experts.  Inference only.
+    captured graph serves a new routing once both are overwritten in place.  At most 1024 experts.  Inference only.  From
+    `MOE_GROUPED_MIN_PAIRS` pairs up the call takes the grouped GEMM of `matmul_mxfp4_experts_grouped_sum`: the same bits.
     """
     what = "matmul_mxfp4_experts_sum"
     x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, True, dtype,
                                                                            routing_weights)
     if T * A == 0:
         return torch.zeros(T, N, dtype=out_dtype, device=x.device)
+    if _takes_grouped(T * A, E):
+        return _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, None)
     out = torch.empty(T, N, dtype=out_dtype, device=x.device)
     step = max(1, _moemlp_native.MAX_PAIRS // A)             # tokens per call
     ws_bytes = _moemlp_native.workspace_bytes(min(T, step), A, N)
@@ -2165,9 +2174,188 @@ def moe_mlp_mxfp4(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor,
     ``matmul_mxfp4_experts_sum(matmul_mxfp4_experts_glu(input, gate_up..., expert_ids, alpha, limit), down..., expert_ids,
     routing_weights, dtype=dtype)`` and nothing more: three launches, the intermediate [T, A, I] in the input's dtype.  The router
     (`expert_ids`, `routing_weights`) stays the caller's.
+    From `MOE_GROUPED_MIN_PAIRS` pairs up both projections run on the grouped GEMM and
+    share one plan of the routing per cut of `MOE_GROUPED_MAX_PAIRS` pairs: the same bits.
     """
+    if (expert_ids.dim() == 2 and expert_ids.is_cuda and not expert_ids.dtype.is_floating_point and gate_up_weight.dim() in (3, 4)
+            and down_weight.dim() in (3, 4) and gate_up_weight.shape[0] == down_weight.shape[0]
+            and _takes_grouped(expert_ids.numel(), gate_up_weight.shape[0])):
+        # the prefill route: one plan per cut over the tokens serves both projections
+        ids, plan = moe_grouped_plan(expert_ids, gate_up_weight.shape[0])
+        h = matmul_mxfp4_experts_grouped_glu(input, gate_up_weight, gate_up_scales, ids, gate_up_bias, alpha, limit, plan=plan)
+        return matmul_mxfp4_experts_grouped_sum(h, down_weight, down_scales, ids, routing_weights, down_bias, dtype, plan=plan)
     h = matmul_mxfp4_experts_glu(input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, alpha, limit)
     return matmul_mxfp4_experts_sum(h, down_weight, down_scales, expert_ids, routing_weights, down_bias, dtype)
+
+
+# ============================================================================= the prefill-sized grouped GEMM over MXFP4 experts
+# libmbnb_moegemm.so (DESIGN.md §32): a plan of the routing built on the device (counts, a stable list of the pairs grouped by
+# expert, a tile table), then one launch per projection for any number of pairs: a workgroup takes 64 listed pairs of one expert
+# against one decode of its weight tile.  A pair's bits are those of the decode launches above, so the three functions of §28 /
+# §29 take this route from MOE_GROUPED_MIN_PAIRS pairs up and only their speed and last_launch() change.
+MOE_GROUPED_MAX_PAIRS = 16384      # pairs of one call: the f32 workspace and the intermediate stay below ~200 MB each at N = 2880
+# The automatic route: matmul_mxfp4_experts, _glu and _sum (and so moe_mlp_mxfp4, moe_block_mxfp4 and the modules) take the grouped GEMM
+# from this many pairs up; None: never.  Measured (profiles/moegemm_bench.jsonl, DESIGN.md §32): at 2048 pairs the grouped route takes
+# 0.43x (E = 32) and 0.62x (E = 128) of the decode route's time; at 1024 pairs 0.62x and 1.19x, so 2048 is the smallest measured count
+# from which it wins at both.
+MOE_GROUPED_MIN_PAIRS: Optional[int] = 2048
+
+
+def _takes_grouped(pairs: int, E: int) -> bool:
+    return MOE_GROUPED_MIN_PAIRS is not None and pairs >= max(1, MOE_GROUPED_MIN_PAIRS) and E <= _moegemm_native.MAX_EXPERTS
+
+
+def _grouped_cuts(T: int, A: int):
+    step = max(1, MOE_GROUPED_MAX_PAIRS // max(1, A))        # tokens per call
+    return [(t0, min(T, t0 + step)) for t0 in range(0, T, step)]
+
+
+def moe_grouped_plan(expert_ids: Tensor, num_experts: int):
+    """
+    The plans of the grouped expert GEMM for `expert_ids` (an integer cuda tensor [T, A]) over `num_experts` experts ->
+    ``(ids, plans)``: the ids as the int32 contiguous tensor the launches read (the caller's own when it is one already) and one
+    plan per cut of at most `MOE_GROUPED_MAX_PAIRS` pairs over the tokens, built on the device in two small launches each.  Pass
+    both on, as `expert_ids` and `plan=`, to the projections that share the routing.  A plan holds the routing it was built from:
+    after `expert_ids` changes in place, build it again.
+    """
+    what = "moe_grouped_plan"
+    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
+        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
+    E = int(num_experts)
+    if not 0 < E <= _moegemm_native.MAX_EXPERTS:
+        raise ValueError(f"{what}: {E} experts, between 1 and {_moegemm_native.MAX_EXPERTS}")
+    _check_device(expert_ids, what)
+    T, A = expert_ids.shape
+    if A > _moegemm_native.MAX_PAIRS:
+        raise ValueError(f"{what}: {A} slots per token exceed the {_moegemm_native.MAX_PAIRS} pairs of one launch")
+    ids = expert_ids
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        ids = ids.to(torch.int32).contiguous()
+    return ids, _grouped_plans(what, ids, T, A, E)
+
+
+def _grouped_plans(what: str, ids: Tensor, T: int, A: int, E: int):
+    plans = []
+    fn = _moegemm_native.lib().mbnb_moegemm_plan
+    with on_device(ids.device):
+        stream = stream_ptr(ids.device)
+        for t0, t1 in _grouped_cuts(T, A):
+            nbytes = _moegemm_native.plan_bytes((t1 - t0) * A, E)
+            plan = torch.empty(nbytes, dtype=torch.uint8, device=ids.device)
+            if (t1 - t0) * A:
+                _moegemm_native.check(fn(ptr(ids[t0:t1]), (t1 - t0) * A, E, ptr(plan), nbytes, stream), what)
+            plans.append(plan)
+    return plans
+
+
+def _grouped_plans_of(what: str, plan, ids: Tensor, T: int, A: int, E: int):
+    """The caller's plans, checked against the cuts of this call, or new ones."""
+    if plan is None:
+        return _grouped_plans(what, ids, T, A, E)
+    cuts = _grouped_cuts(T, A)
+    if not isinstance(plan, (list, tuple)) or len(plan) != len(cuts) or any(
+            not isinstance(q, Tensor) or q.dtype != torch.uint8 or q.device != ids.device or not q.is_contiguous()
+            or q.numel() < _moegemm_native.plan_bytes((t1 - t0) * A, E) for q, (t0, t1) in zip(plan, cuts)):
+        raise ValueError(f"{what}: plan must be what moe_grouped_plan returned for these expert_ids and {E} experts: "
+                         f"{len(cuts)} uint8 tensor(s) on {ids.device}")
+    return list(plan)
+
+
+def _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, plan):
+    per_slot = x.dim() == 3
+    out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
+    if T * A == 0:
+        return out
+    plans = _grouped_plans_of(what, plan, ids, T, A, E)
+    fn = _moegemm_native.lib().mbnb_moegemm_experts
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
+            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
+                                     ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode,
+                                     ptr(q), q.numel(), stream), what)
+    return out
+
+
+def _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, plan):
+    I = N // 2
+    out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
+    if T * A == 0:
+        return out
+    plans = _grouped_plans_of(what, plan, ids, T, A, E)
+    fn = _moegemm_native.lib().mbnb_moegemm_gate_up_glu
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
+            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, I, ptr(ids[t0:t1]), ptr(b),
+                                     0 if b is None else _native.DTYPE_CODE[b.dtype], alpha, limit, ptr(out[t0:t1]), ocode, ptr(q), q.numel(),
+                                     stream), what)
+    return out
+
+
+def _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, plan):
+    if T * A == 0:
+        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
+    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
+    plans = _grouped_plans_of(what, plan, ids, T, A, E)
+    cuts = _grouped_cuts(T, A)
+    ws_bytes = _moegemm_native.workspace_bytes((cuts[0][1] - cuts[0][0]) * A, N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    fn = _moegemm_native.lib().mbnb_moegemm_down_sum
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(cuts, plans):
+            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b),
+                                     0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(rw[t0:t1]), _native.DTYPE_CODE[rw.dtype],
+                                     ptr(out[t0:t1]), ocode, ptr(ws), ws_bytes, ptr(q), q.numel(), stream), what)
+    return out
+
+
+def matmul_mxfp4_experts_grouped(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                                 dtype: Optional[torch.dtype] = None, plan=None) -> Tensor:
+    """
+    `matmul_mxfp4_experts` on the grouped GEMM of libmbnb_moegemm.so, at any number of pairs: the same operands, checks, errors and
+    result BITS -> ``[T, A, N]``.  The routing is planned on the device (two small launches, no host round trip), then one launch
+    of `k_mx_experts_grouped` serves up to `MOE_GROUPED_MAX_PAIRS` pairs (more are cut over the tokens): every expert's pairs are
+    taken 64 at a time against one decode of the weight tile.  `plan`: what `moe_grouped_plan` returned for these ids, to share
+    one plan between projections; None builds it here.  Ids are read on the device, so a captured graph serves a new routing once
+    `expert_ids` is overwritten in place (the plan launches are part of the graph when they are captured with the call).  At
+    most 1024 experts.  Inference only.
+    """
+    what = "matmul_mxfp4_experts_grouped"
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
+                                                                          None, dtype)
+    return _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, plan)
+
+
+def matmul_mxfp4_experts_grouped_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                                     alpha: float = 1.702, limit: float = 7.0, dtype: Optional[torch.dtype] = None, plan=None) -> Tensor:
+    """
+    `matmul_mxfp4_experts_glu` on the grouped GEMM, at any number of pairs: the same operands, checks, errors and result bits ->
+    ``[T, A, I]``; the gated activation is the epilogue of the one launch per cut.  `plan` as in `matmul_mxfp4_experts_grouped`.
+    """
+    what = "matmul_mxfp4_experts_grouped_glu"
+    alpha, limit = float(alpha), float(limit)
+    if not math.isfinite(alpha) or not limit > 0:
+        raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
+    if weight.dim() in (3, 4) and weight.shape[1] % 2:
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
+                                                                          False, dtype)
+    return _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, plan)
+
+
+def matmul_mxfp4_experts_grouped_sum(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
+                                     bias: Optional[Tensor] = None, dtype: Optional[torch.dtype] = None, plan=None) -> Tensor:
+    """
+    `matmul_mxfp4_experts_sum` on the grouped GEMM, at any number of pairs: the same operands, checks, errors and result bits ->
+    ``[T, N]``; the projection goes in f32 into a workspace that is a ``torch.empty`` of this call (at most `MOE_GROUPED_MAX_PAIRS`
+    rows), the routed sum over the slots follows as a second launch.  `plan` as in `matmul_mxfp4_experts_grouped`.
+    """
+    what = "matmul_mxfp4_experts_grouped_sum"
+    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
+                                                                           True, dtype, routing_weights)
+    return _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, plan)
 
 
 # ============================================================================= the router of the mixture-of-experts block
