@@ -166,3 +166,50 @@ OFFSETS = [dict(x=0, w_codes=0, w_scales=0, ids=0, out=0, bias=0), dict(x=16, w_
 
 # the Python surface: more pairs than one launch
 CUT_SHAPE = (300, 4, 3, 5, 32)                      # T, A, E, N, K
+
+
+# ---------------------------------------------------------------- the K walk of the decode tile
+# K has KB = K / 32 blocks and s = ceil(KB / 4) k-steps; step c runs on wave c % 8 in that wave's pass c // 8 (tile_walk requests two
+# passes per outer iteration).  The last step, c = s - 1, holds KB - 4 (s - 1) blocks: the others of its four are read from the
+# clamped address and zeroed in registers.
+WALK_KS = (
+    352,                     # s = 3,  last step 3 blocks, wave 2, pass 0
+    448,                     # s = 4,  last step 2 blocks, wave 3, pass 0
+    992,                     # s = 8,  last step 3 blocks, wave 7, pass 0
+    1024,                    # s = 8,  last step whole,    wave 7, pass 0: one whole round
+    1216,                    # s = 10, last step 2 blocks, wave 1, pass 1
+    2016,                    # s = 16, last step 3 blocks, wave 7, pass 1
+    2048,                    # s = 16, last step whole,    wave 7, pass 1: two whole rounds
+    2880,                    # s = 23, last step 2 blocks, wave 6, pass 2: the model's size (gpt-oss, H = I = 2880)
+    3104,                    # s = 25, last step 1 block,  wave 0, pass 3: tile_walk's second outer iteration with a live u = 1 step
+)
+WALK_NONFINITE_KS = (992, 2880)                     # the tail off wave 0: where the 0xFF bytes, Inf and NaN are planted on it
+
+
+def walk_of(K):
+    """K -> dict(steps, tail: the blocks of the last step, first: the first block of the last step, wave, passes: the pass of the last step)"""
+    KB = K // 32
+    steps = -(-KB // 4)
+    return dict(steps=steps, tail=KB - 4 * (steps - 1), first=4 * (steps - 1), wave=(steps - 1) % 8, passes=(steps - 1) // 8)
+
+
+# k_mx_experts at every K of the walk: (E, N, K, T, A, pairs per expert, x dtype, out dtype, bias, per-slot input), the layout of
+# EXACT_CASES.  N = 17 is two 16-row tiles, the second with one live column; 33 pairs are three passes of the pair list.
+WALK_SEED = 100                                     # exact_operands(case, WALK_SEED + i): seeds no other table uses
+WALK_CASES = [(3, 17, K, 11, 3, (17, 0, 16), X16[i % 2], DTYPES[i % 3], (i // 2) % 2 == 0, (i // 3) % 2 == 1) for i, K in enumerate(WALK_KS)]
+
+
+def walk_nan_blocks(K):
+    """the blocks that get a 0xFF byte: the first block of the last step and block KB - 1"""
+    return tuple(sorted({walk_of(K)["first"], K // 32 - 1}))
+
+
+def walk_bad_ks(K):
+    """the k that get an Inf or a NaN activation: the first k of the last step and K - 1"""
+    return (32 * walk_of(K)["first"], K - 1)
+
+
+def walk_nan_operands(K):
+    """(x float64 [T, K], w float64 [E, N, K], ids) of NAN_SHAPE's E, N, T, A at a K of the walk"""
+    E, N, _, T, A = NAN_SHAPE
+    return emul.lossless(T, K, seed=27100 + K), emul.lossless(E * N, K, seed=27101 + K).reshape(E, N, K), nan_operands()[2]

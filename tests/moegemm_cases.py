@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from mps_bitsandbytes_amd import _moegemm_native as gn
-from tests import moe_cases
+from tests import moe_cases, moemlp_cases, mx_emul as emul
 
 R, C = gn.ROW_TILE, gn.TILE_N
 X16, DTYPES = moe_cases.X16, moe_cases.DTYPES
@@ -176,6 +176,189 @@ def random_routing(ta, routing):
 # out, bias and rw
 OFFSETS = [dict(x=0, w_codes=0, w_scales=0, ids=0, out=0, bias=0, rw=0, ws=0, plan=0), dict(x=16, w_codes=32, w_scales=1, ids=1, out=1, bias=1, rw=1, ws=16, plan=48),
            dict(x=48, w_codes=16, w_scales=3, ids=3, out=3, bias=2, rw=3, ws=32, plan=16), dict(x=32, w_codes=48, w_scales=2, ids=2, out=5, bias=3, rw=2, ws=48, plan=32)]
+
+# ---------------------------------------------------------------- the K walk (tests/moe_cases.py WALK_KS), the three forms
+# E = 3 with counts (R + 1, 0, 3): expert 0 has a full row tile and a one-row tile.  Plain: N = C + 1, the layout of EXACT_CASES.
+# GLU: N = C + 2 (I = C / 2 + 1), the layout of moemlp_cases.GLU_CASES.  Down + sum: N = C + 1, the layout of moemlp_cases.SUM_CASES.
+# Every one has a second column tile of one live column (plain, down) or one live (gate, up) pair (GLU).
+WALK_KS, WALK_NONFINITE_KS, walk_of = moe_cases.WALK_KS, moe_cases.WALK_NONFINITE_KS, moe_cases.walk_of
+WALK_SEED = 200                                                # the operands of case i: seeds WALK_SEED + i of the generators
+_WALK_T, _WALK_A, _WALK_COUNTS = 17, 4, (R + 1, 0, 3)
+WALK_CASES = [(3, C + 1, K, _WALK_T, _WALK_A, _WALK_COUNTS, X16[i % 2], DTYPES[i % 3], (i // 2) % 2 == 0, (i // 3) % 2 == 1) for i, K in enumerate(WALK_KS)]
+WALK_GLU_CASES = [(3, C // 2 + 1, K, _WALK_T, _WALK_A, _WALK_COUNTS, X16[(i + 1) % 2], DTYPES[(i + 1) % 3], (i // 2) % 2 == 1, (moemlp_cases.LIMIT, moemlp_cases.INF)[(i // 3) % 2])
+                  for i, K in enumerate(WALK_KS)]
+WALK_SUM_CASES = [(3, C + 1, K, _WALK_T, _WALK_A, _WALK_COUNTS, X16[i % 2], DTYPES[(i + 2) % 3], (i // 2) % 2 == 0, DTYPES[(i + 1) % 3]) for i, K in enumerate(WALK_KS)]
+glu_operands, sum_operands = moemlp_cases.glu_operands, moemlp_cases.sum_operands
+
+# the bit rule at the model's K and at a tail on wave 7: (N, K) of the weights, E = RANDOM_E, P = 70, the uniform routing
+WALK_RANDOM_WEIGHTS = ((17, 2880), (C + 1, 992))
+WALK_RANDOM_PAIRS = RANDOM_PAIRS[0]
+
+# ---------------------------------------------------------------- past one column tile in the GLU and down forms: K = 160
+# (form, N): N on either side of the column tile and past two of them; for GLU that is I = 23, 24, 25, 49: both parities of I, and
+# the tile edge on either side of a (gate, up) pair.  One routing: counts on the row-tile edges, a last expert that pads the call
+# to T x A, and the four ids outside [0, E).
+TILE_K = 160
+TILE_CASES = [("glu", n) for n in (C - 2, C, C + 2, 2 * C + 2)] + [("down", n) for n in (C - 1, C, C + 1, 2 * C + 1)]
+TILE_E, TILE_T, TILE_A = 6, 50, 4
+TILE_COUNTS = (0, 1, R - 1, R, R + 1, 3)
+TILE_ALL_OUTSIDE = (("glu", 2 * C + 2), ("plain", 2 * C + 1), ("down", 2 * C + 1))
+
+
+def tile_ids():
+    """int32 [TILE_T, TILE_A]: TILE_COUNTS and moe_cases.OUT_OF_RANGE's four ids (E standing for its E) at seeded places"""
+    outside = tuple(TILE_E if v == moe_cases.IDS_SHAPE[0] else v for v in moe_cases.OUT_OF_RANGE)
+    return _from_counts(TILE_COUNTS, outside, 44000).reshape(TILE_T, TILE_A)
+
+
+def tile_operands(form, N):
+    """(rows float64: x [T, K] for GLU, h [T, A, K] otherwise; w float64 [E, N, K]; bias float64 [E, N], never zero, four times as
+    wide for GLU so that the pre-activations lie on both sides of the limit; ids; rw float64 [T, A])"""
+    T, A, E, K = TILE_T, TILE_A, TILE_E, TILE_K
+    rows = emul.lossless(T if form == "glu" else T * A, K, seed=44100 + N) * 0.125
+    w = emul.lossless(E * N, K, seed=44200 + N).reshape(E, N, K)
+    rng = np.random.default_rng(44300 + N)
+    bias = rng.integers(1, 9, size=(E, N)).astype(np.float64) * rng.choice((-1.0, 1.0), size=(E, N))
+    rw = np.random.default_rng(44400 + N).integers(1, 33, size=(T, A)) / 64.0
+    return (rows if form == "glu" else rows.reshape(T, A, K)), w, bias * (4.0 if form == "glu" else 1.0), tile_ids(), rw
+
+
+# ---------------------------------------------------------------- many experts, the three forms: (E, N, K, T, A, counts)
+# moemlp_cases' MAX_EXPERTS row mirrored: sparse counts that include the lowest and the highest expert.  The GLU form needs an even
+# N: it runs at N + 1 (E = 128: C + 2, past the column tile by one pair; MAX_EXPERTS: I = 1).
+MANY_CASES = [
+    (128, C + 1, 64, 40, 4, _sparse(128, e0=3, e1=1, e63=R + 1, e64=R, e126=2, e127=160 - 2 * R - 7)),
+    (gn.MAX_EXPERTS, 1, 32, 8, 4, _sparse(gn.MAX_EXPERTS, e0=3, e63=1, e64=17, e65=2, e511=1, e960=7, e1023=1)),
+]
+
+
+def many_operands(case, index, form):
+    """(rows, w [E, N or N + 1, K], bias, ids, rw): lossless, the layout of tile_operands"""
+    E, N, K, T, A, counts = case
+    n = N + 1 if form == "glu" else N
+    rows = emul.lossless(T if form == "glu" else T * A, K, seed=45000 + 8 * index) * 0.125
+    w = emul.lossless(E * n, K, seed=45001 + 8 * index + len(form)).reshape(E, n, K)
+    bias = np.random.default_rng(45002 + 8 * index).integers(1, 9, size=(E, n)).astype(np.float64)
+    rw = np.random.default_rng(45003 + 8 * index).integers(1, 33, size=(T, A)) / 64.0
+    return (rows if form == "glu" else rows.reshape(T, A, K)), w, bias, moe_cases.ids_from_counts(counts, T, A, seed=45004 + index), rw
+
+
+# ---------------------------------------------------------------- the references of the three forms, and the kernel restated
+def same_values(a, b):
+    """NaN in the same places, the same values elsewhere"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool((np.isnan(a) == np.isnan(b)).all()) and bool((a[~np.isnan(a)] == b[~np.isnan(b)]).all())
+
+
+def reference(form, x, codes, scales, ids, bias, alpha=0.0, limit=moemlp_cases.INF, rw=None):
+    """float64 over moe_cases.decode_experts, then the form's own chain in f32: `plain` float64 [P, N]; `glu` f32 [P, N / 2]
+    (moemlp_cases.glu_f32 over the pre-activations rounded once to f32; the rows of the pairs outside [0, E): +0.0); `down` f32
+    [T, N] (moemlp_cases.routed_sum_f32 over the same)"""
+    E = codes.shape[0]
+    pre = moe_cases.reference_f64(x, moe_cases.decode_experts(codes, scales), bias, ids)
+    if form == "plain":
+        return pre
+    with np.errstate(over="ignore", invalid="ignore"):
+        pre32 = pre.astype(np.float32)
+    if form == "down":
+        return moemlp_cases.routed_sum_f32(pre32, rw, ids, E)
+    flat = ids.reshape(-1)
+    h = moemlp_cases.glu_f32(*moemlp_cases.split(pre32), alpha, limit)
+    h[(flat < 0) | (flat >= E)] = 0.0
+    return h
+
+
+MUTANTS = ("steps_floor", "tail_keeps_x_and_scale", "tail_keeps_w", "tail_only_wave_idle", "glu_column_forgets_n0", "zeros_on_column_tile_0",
+           "workspace_stride_of_a_tile", "tail_past_wave_1", "three_passes")
+ZERO_THREADS = 512                                             # of the workgroup: ZERO_THREADS // columns rows of +0.0 per pass
+
+
+def grouped_as_kernel(x, codes, scales, ids, bias, form, mutate=None, alpha=0.0, limit=moemlp_cases.INF, rw=None):
+    """reference() restated along k_mx_experts_grouped's structure (csrc/moegemm_kernels.hip): the plan's tiles of R listed pairs
+    against column tiles of C weight rows; per workgroup the k-steps of four blocks dealt to eight waves, the blocks of the last
+    step that lie past K read from the clamped block and zeroed (activation, weight) or set to 2^0 (scale); the eight partial sums
+    added from +0.0 in wave order; the three epilogues with their column arithmetic, and the rows of +0.0.  An output element no
+    workgroup wrote is NaN here.  Unmutated it equals reference() on every exact table (tests/test_moegemm_host.py).  `mutate`:
+      "steps_floor"                 steps = KB // 4: the ragged last step is dropped
+      "tail_keeps_x_and_scale"      the blocks past K keep the clamped block's activation and scale byte
+      "tail_keeps_w"                the weight dwords of the lane groups with 4 c + g >= KB are not zeroed
+      "tail_only_wave_idle"         a wave whose only step is the ragged last step does nothing
+      "glu_column_forgets_n0"       the GLU store column is (16 j + fr) / 2, without n0 / 2
+      "zeros_on_column_tile_0"      the rows of +0.0 are written by the workgroups of column tile 0 only
+      "workspace_stride_of_a_tile"  the workspace row stride is the width of column tile 0, min(N, C), in place of N
+      "tail_past_wave_1"            the ragged last step is dropped when it falls on a wave past wave 1
+      "three_passes"                a wave takes at most three steps"""
+    assert mutate is None or mutate in MUTANTS, mutate
+    T, A = ids.shape
+    P, (E, N, _), K = T * A, codes.shape, x.shape[-1]
+    KB, glu = K // 32, form == "glu"
+    rows = moe_cases.pair_rows(np.asarray(x, dtype=np.float64), A)
+    c4 = emul.unpack(codes.reshape(E * N, -1), "fp4").astype(np.int64)
+    wval = np.where(c4 & 8, -emul.FP4_GRID[c4 & 7], emul.FP4_GRID[c4 & 7]).reshape(E, N, K)
+    sbytes = np.asarray(scales, dtype=np.int64)
+    plan = plan_reference(ids, E)
+    tiles, order, n_tiles, n_listed, mt = plan["tiles"], plan["sorted"], plan["n_tiles"], plan["n_listed"], max_tiles(P, E)
+    width = N // 2 if glu else N
+    stride = min(N, C) if mutate == "workspace_stride_of_a_tile" else N
+    out = np.full(P * max(width, C), np.nan)                   # flat; the first P * width elements are the output (or the workspace)
+    whole = -(-KB // 4)
+    steps = KB // 4 if mutate == "steps_floor" else whole
+    ragged = whole - 1 if KB % 4 else -1                       # the index of the ragged last step
+    with np.errstate(invalid="ignore", over="ignore"):
+        for tile in range(mt):
+            for n0 in range(0, N, C):
+                if form != "down" and not (mutate == "zeros_on_column_tile_0" and n0):
+                    zcols = C // 2 if glu else C
+                    zrows = ZERO_THREADS // zcols
+                    cols = (n0 // 2 if glu else n0) + np.arange(zcols)
+                    cols = cols[cols < width]
+                    for r in range(zrows):
+                        for i in range(n_listed + tile * zrows + r, P, mt * zrows):
+                            out[order[i] * width + cols] = 0.0
+                if tile >= n_tiles:
+                    continue
+                e, first, count = (int(v) for v in tiles[tile])
+                pairs = order[first:first + count].astype(np.int64)
+                ncols = min(C, N - n0)
+                xr, wv, sv = rows[pairs], wval[e, n0:n0 + ncols], sbytes[e, n0:n0 + ncols]
+                acc, ff = np.zeros((8, count, ncols)), np.zeros(ncols, dtype=bool)
+                for c in range(steps):
+                    wave = c % 8
+                    if c == ragged and ((mutate == "tail_only_wave_idle" and c < 8) or (mutate == "tail_past_wave_1" and wave > 1)):
+                        continue
+                    if mutate == "three_passes" and c // 8 >= 3:
+                        continue
+                    for q in range(4):
+                        inside = 4 * c + q < KB
+                        b = 4 * c + q if inside else KB - 1
+                        xq, wq, byte = xr[:, 32 * b:32 * b + 32], wv[:, 32 * b:32 * b + 32], sv[:, b]
+                        if not inside:
+                            if mutate != "tail_keeps_x_and_scale":
+                                xq, byte = np.zeros_like(xq), np.full_like(byte, 127)
+                            if mutate != "tail_keeps_w":
+                                wq = np.zeros_like(wq)
+                        ff |= byte == 255
+                        d = xq @ wq.T if np.isfinite(xq).all() else (xq[:, None, :] * wq[None, :, :]).sum(axis=2)
+                        acc[wave] += d * np.ldexp(1.0, np.where(byte == 255, 127, byte) - 127)[None, :]       # one FMA by the scale per block
+                total = np.zeros((count, ncols))
+                for wave in range(8):
+                    total = total + acc[wave]
+                pre = total if bias is None else total + np.asarray(bias, dtype=np.float64)[e, n0:n0 + ncols][None, :]
+                pre = np.where(ff[None, :], np.nan, pre)
+                if glu:                                            # ncols is even: (gate, up) pairs never straddle a column tile
+                    pre32 = pre.astype(np.float32)
+                    h = moemlp_cases.glu_f32(pre32[:, 0::2], pre32[:, 1::2], alpha, limit)
+                    col = (0 if mutate == "glu_column_forgets_n0" else n0 // 2) + np.arange(ncols // 2)
+                    out[pairs[:, None] * width + col[None, :]] = h
+                else:
+                    out[pairs[:, None] * (stride if form == "down" else width) + (n0 + np.arange(ncols))[None, :]] = pre
+    res = out[:P * width].reshape(P, width)
+    if form == "plain":
+        return res
+    if glu:
+        return res.astype(np.float32)
+    return moemlp_cases.routed_sum_f32(res.astype(np.float32), rw, ids, E)
+
 
 # the Python surface: more pairs than one call of the grouped route, on a tiny N and K: T, A, E, N, K
 CUT_A = 4

@@ -236,3 +236,11 @@ OFFSETS = [dict(x=0, w_codes=0, w_scales=0, ids=0, out=0, bias=0, rw=0, ws=0), d
            dict(x=48, w_codes=16, w_scales=3, ids=3, out=3, bias=2, rw=3, ws=48), dict(x=32, w_codes=48, w_scales=2, ids=2, out=5, bias=3, rw=2, ws=32)]
 
 CUT_SHAPE = (300, 4, 3, 32, 32)                                # the Python surface, more pairs than one call: T, A, E, I, H
+
+# ---------------------------------------------------------------- the K walk (tests/moe_cases.py WALK_KS), both epilogues
+# The routing of moe_cases.WALK_CASES: 33 pairs, counts (17, 0, 16).  GLU: I = 9 (two 8-output tiles, the second with one live
+# output), the layout of GLU_CASES.  Down + sum: N = 17, the layout of SUM_CASES.
+WALK_KS, WALK_NONFINITE_KS, walk_of = moe_cases.WALK_KS, moe_cases.WALK_NONFINITE_KS, moe_cases.walk_of
+WALK_SEED = 100                                                # glu_operands / sum_operands(case, WALK_SEED + i)
+WALK_GLU_CASES = [(3, 9, K, 11, 3, (17, 0, 16), X16[i % 2], DTYPES[i % 3], (i // 2) % 2 == 0, (LIMIT, INF)[(i // 3) % 2]) for i, K in enumerate(WALK_KS)]
+WALK_SUM_CASES = [(3, 17, K, 11, 3, (17, 0, 16), X16[(i + 1) % 2], DTYPES[(i + 1) % 3], (i // 2) % 2 == 1, DTYPES[(i + 2) % 3]) for i, K in enumerate(WALK_KS)]

@@ -84,6 +84,18 @@ def test_lossless_operands_bit_for_bit(index):
                offsets=cases.OFFSETS[index % len(cases.OFFSETS)])
 
 
+@pytest.mark.parametrize("index", range(len(cases.WALK_CASES)), ids=lambda i: f"K{cases.WALK_KS[i]}")
+def test_lossless_operands_at_every_k_of_the_walk_bit_for_bit(index):
+    """tests/moe_cases.py WALK_KS: ragged last steps of 1, 2 and 3 blocks and whole ones, on wave 0, a middle wave and wave 7, in a
+    wave's first to fourth pass"""
+    case = cases.WALK_CASES[index]
+    x_dtype, out_dtype = case[6], case[7]
+    x64, w64, bias64, ids = cases.exact_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    _exact_run(x64, x_dtype, w_codes, w_scales, ids, bias64, cases.DTYPES[(index + 1) % 3], out_dtype, f"walk {case}",
+               offsets=cases.OFFSETS[index % len(cases.OFFSETS)])
+
+
 # ----------------------------------------------------------------------------- B. ids outside [0, E)
 def test_ids_outside_the_experts_give_rows_of_plus_zero_and_leave_every_other_pair_alone():
     E, N, K, T, A = cases.IDS_SHAPE
@@ -175,15 +187,15 @@ def test_every_pair_has_the_bits_of_the_weight_only_linear_whatever_else_is_in_t
 
 
 # ----------------------------------------------------------------------------- D. NaN and Inf
-def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only():
-    E, N, K, T, A = cases.NAN_SHAPE
-    x64, w64, ids = cases.nan_operands()
+def _nan_bytes(shape, x64, w64, ids, blocks):
+    """a 0xFF byte in each of `blocks` in turn, with the activations of that block as they are and zeroed -> (codes, scales, clean, hit)"""
+    E, N, K, T, A = shape
     w_codes, w_scales = cases.quantize_experts(w64)
     clean = _exact_run(x64, torch.bfloat16, w_codes, w_scales, ids, None, None, torch.float32, "clean")
     hit = torch.zeros(T * A, N, dtype=torch.bool)
     hit[torch.from_numpy(ids.reshape(-1) == cases.NAN_EXPERT), cases.NAN_COLUMN] = True
     assert 0 < int(hit.sum()) < T * A
-    for i, b in enumerate(cases.NAN_BLOCKS):
+    for i, b in enumerate(blocks):
         planted = w_scales.copy()
         planted[cases.NAN_EXPERT, cases.NAN_COLUMN, b] = 255
         for zero_x in (False, True):
@@ -194,6 +206,13 @@ def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only(
             y = run_experts(cases.to_dtype(xb, (torch.bfloat16, torch.float16)[i % 2]), w_codes, planted, ids, None, torch.float32, FILLS[(i + zero_x) % 2])
             assert bool(torch.isnan(y[hit]).all()), (b, zero_x)
             _assert_bits(y[~hit], want[~hit], f"0xFF in block {b}, x block zero: {zero_x}: every other element")
+    return w_codes, w_scales, clean, hit
+
+
+def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only():
+    E, N, K, T, A = cases.NAN_SHAPE
+    x64, w64, ids = cases.nan_operands()
+    w_codes, w_scales, clean, hit = _nan_bytes(cases.NAN_SHAPE, x64, w64, ids, cases.NAN_BLOCKS)
     planted = w_scales.copy()
     planted[cases.NAN_EXPERT, cases.NAN_COLUMN, list(cases.NAN_BLOCKS)] = 255
     bias = torch.ones(E, N)
@@ -202,15 +221,14 @@ def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only(
     _assert_bits(y[~hit], (clean + 1.0).to(torch.bfloat16)[~hit], "several 0xFF bytes, a bias: every other element")
 
 
-@pytest.mark.parametrize("x_dtype", cases.X16, ids=_name)
-def test_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
-    E, N, K, T, A = cases.NAN_SHAPE
-    x64, w64, ids = cases.nan_operands()
+def _bad_activations(shape, x64, w64, ids, ks, x_dtype):
+    """an Inf, a -Inf and a NaN at each k of `ks` of one token's row in turn"""
+    E, N, K, T, A = shape
     w_codes, w_scales = cases.quantize_experts(w64)
     clean = _round_once(cases.reference_f64(x64, w64, None, ids), torch.float32).reshape(T, A, N)
     other = torch.tensor([t != cases.X_BAD_TOKEN for t in range(T)])
     n = 0
-    for ki, k in enumerate(cases.X_BAD_KS):
+    for ki, k in enumerate(ks):
         for vi, v in enumerate(cases.X_BAD_VALUES):
             xb = x64.copy()
             xb[cases.X_BAD_TOKEN, k] = v
@@ -222,6 +240,22 @@ def test_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
             _assert_bits(y[other], clean[other], f"{v} at k = {k}: the other tokens")
             n += int(np.isinf(want).any())
     assert n > 0
+
+
+@pytest.mark.parametrize("x_dtype", cases.X16, ids=_name)
+def test_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
+    x64, w64, ids = cases.nan_operands()
+    _bad_activations(cases.NAN_SHAPE, x64, w64, ids, cases.X_BAD_KS, x_dtype)
+
+
+@pytest.mark.parametrize("K", cases.WALK_NONFINITE_KS)
+def test_nan_bytes_inf_and_nan_on_a_ragged_last_step_off_wave_0(K):
+    """The 0xFF byte on the first block of the last step and on block KB - 1, the Inf and the NaN at the first k of the last step and
+    at k = K - 1, where that step runs on wave 7 (K = 992) and on wave 6 in its third pass (K = 2880, the model's size)"""
+    E, N, _, T, A = cases.NAN_SHAPE
+    x64, w64, ids = cases.walk_nan_operands(K)
+    _nan_bytes((E, N, K, T, A), x64, w64, ids, cases.walk_nan_blocks(K))
+    _bad_activations((E, N, K, T, A), x64, w64, ids, cases.walk_bad_ks(K), cases.X16[cases.WALK_NONFINITE_KS.index(K) % 2])
 
 
 # ----------------------------------------------------------------------------- E. scale bytes

@@ -6,6 +6,8 @@ older than these: mbnb_moe_mxfp4_experts, mbnb_moemlp_gate_up_glu and mbnb_moeml
   1  the plan, integer for integer                  2  lossless operands against float64 rounded once
   3  the bit rule: every pair, the GLU form and the down + sum form against the decode launches; the elementwise bound
   4  0xFF scale bytes, Inf / NaN rows, scale bytes from end to end, ids outside [0, E)
+  4b the GLU and down + sum forms past one column tile, every id outside across every column tile, 128 and 1024 experts
+     (2 to 4 also at every K of moe_cases.WALK_KS: the ragged last step on every kind of wave and pass, the model's K = 2880)
   5  the Python surface: the three functions, the cut, the automatic route, a captured graph"""
 import numpy as np
 import pytest
@@ -42,6 +44,14 @@ def _placed(name, t, fill, offset_bytes):
 
 def _is_plus_zero(t):
     return bool((t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16) == 0).all())
+
+
+def _assert_bits_nan(got, want, what):
+    """every NaN on one bit pattern: which NaN an Inf * 0 gives is the only thing numpy and the device may differ in"""
+    got, want = got.clone(), want.clone()
+    got[torch.isnan(got)] = float("nan")
+    want[torch.isnan(want)] = float("nan")
+    _assert_bits(got, want, what)
 
 
 def _check_guards(guards, what):
@@ -200,6 +210,60 @@ def test_lossless_operands_bit_for_bit(index):
         _assert_bits(y, want, f"exact {case}, fill {fill:#x}")
 
 
+def _walk_id(i):
+    return f"K{cases.WALK_KS[i]}"
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_CASES)), ids=_walk_id)
+def test_lossless_operands_at_every_k_of_the_walk_bit_for_bit(index):
+    """tests/moe_cases.py WALK_KS through the kernel's own K walk: a full row tile and a one-row tile, a second column tile of one
+    live column; ragged last steps of 1 to 3 blocks and whole ones on wave 0, middle waves and wave 7, in a wave's first to fourth pass"""
+    case = cases.WALK_CASES[index]
+    x_dtype, out_dtype = case[6], case[7]
+    x64, w64, bias64, ids = cases.exact_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    want = _round_once(cases.reference("plain", x64, w_codes, w_scales, ids, bias64), out_dtype)
+    bias = None if bias64 is None else cases.to_dtype(bias64, cases.DTYPES[(index + 1) % 3])
+    for fill in FILLS:
+        y = run_grouped("plain", cases.to_dtype(x64, x_dtype), w_codes, w_scales, ids, bias, out_dtype, fill, cases.OFFSETS[index % len(cases.OFFSETS)])
+        _assert_bits(y, want, f"walk {case}, fill {fill:#x}")
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_GLU_CASES)), ids=_walk_id)
+def test_glu_with_alpha_zero_at_every_k_of_the_walk_bit_for_bit(index):
+    """With alpha = 0 every step of the chain is a correctly rounded IEEE operation (tests/moemlp_cases.py glu_f32), so the yardstick
+    is float64 over the decoded weights, rounded once to the f32 pre-activation, through that chain.  N = C + 2: the second column
+    tile holds one (gate, up) pair"""
+    case = cases.WALK_GLU_CASES[index]
+    E, I, K, T, A, _, x_dtype, out_dtype, _, limit = case
+    x64, w64, bias64, ids = cases.glu_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    want = _round_once(cases.reference("glu", x64, w_codes, w_scales, ids, bias64, 0.0, limit).astype(np.float64), out_dtype)
+    bias = None if bias64 is None else cases.to_dtype(bias64, cases.DTYPES[(index + 2) % 3])
+    for fill in FILLS:
+        h = run_grouped("glu", cases.to_dtype(x64, x_dtype), w_codes, w_scales, ids, bias, out_dtype, fill, cases.OFFSETS[(index + 1) % len(cases.OFFSETS)],
+                        alpha=0.0, limit=limit)
+        _assert_bits(h, want, f"walk glu {case[:5]}, fill {fill:#x}")
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_SUM_CASES)), ids=_walk_id)
+def test_down_and_routed_sum_at_every_k_of_the_walk_bit_for_bit(index):
+    """float64 over the decoded weights, rounded once to the f32 workspace, through tests/moemlp_cases.py routed_sum_f32 (one fmaf per
+    slot, in slot order): exact.  N = C + 1: the second column tile's rows of the workspace hold one column"""
+    case = cases.WALK_SUM_CASES[index]
+    E, N, K, T, A, _, h_dtype, out_dtype, _, rw_dtype = case
+    h64, w64, bias64, ids, rw64 = cases.sum_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    rw = cases.to_dtype(rw64, rw_dtype)
+    assert (rw.double().numpy() == rw64).all()
+    want = _round_once(cases.reference("down", h64, w_codes, w_scales, ids, bias64, rw=rw64).astype(np.float64), out_dtype)
+    bias = None if bias64 is None else cases.to_dtype(bias64, cases.DTYPES[index % 3])
+    for i, fill in enumerate(FILLS):
+        out = run_grouped("down", cases.to_dtype(h64, h_dtype), w_codes, w_scales, ids, bias, out_dtype, fill, cases.OFFSETS[(index + 2) % len(cases.OFFSETS)],
+                          rw=rw, ws_fill=FILLS[(index + i) % 2])
+        _assert_bits_nan(out, want, f"walk down + sum {case[:5]}, fill {fill:#x}")
+
+
 # ----------------------------------------------------------------------------- 3. the bit rule
 _WEIGHTS = {}
 
@@ -216,7 +280,17 @@ def _weights(nk):
 
 @pytest.mark.parametrize("index", range(len(cases.RANDOM_CASES)), ids=lambda i: "-".join(_name(v) for v in cases.RANDOM_CASES[i]))
 def test_every_pair_has_the_bits_of_the_decode_launches(index):
-    nk, ta, routing = cases.RANDOM_CASES[index]
+    _bit_rule(*cases.RANDOM_CASES[index], index)
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_RANDOM_WEIGHTS)), ids=lambda i: _name(cases.WALK_RANDOM_WEIGHTS[i]))
+def test_every_pair_has_the_bits_of_the_decode_launches_at_the_models_k_and_on_a_wave_7_tail(index):
+    """(17, 2880) and (C + 1, 992): the three forms against the decode launches bit for bit, and both inside the elementwise bounds
+    against float64 without a factor (the GLU form: tests/moemlp_cases.py within_glu_bound over the f32 pre-activations)"""
+    _bit_rule(cases.WALK_RANDOM_WEIGHTS[index], cases.WALK_RANDOM_PAIRS, "uniform", index, glu_bound=True)
+
+
+def _bit_rule(nk, ta, routing, index, glu_bound=False):
     (N, K), (T, A), E = nk, ta, cases.RANDOM_E
     x_dtype = cases.X16[index % 2]
     w_codes, w_scales, wq, bias = _weights(nk)
@@ -250,6 +324,16 @@ def test_every_pair_has_the_bits_of_the_decode_launches(index):
         h = run_grouped("glu", x, w_codes[:, :n2], w_scales[:, :n2], ids, gb, out_dtype, FILLS[index % 2], off)
         _assert_bits(h, want, f"{nk} {ta} {routing} -> {out_dtype}: the GLU form against mbnb_moemlp_gate_up_glu")
         assert _is_plus_zero(h[~listed])
+        if glu_bound:
+            pre = yard_experts(x, w_codes[:, :n2], w_scales[:, :n2], ids, gb, torch.float32).numpy()[listed.numpy()]
+            assert (np.abs(pre) > LIMIT).any() and (np.abs(pre) < LIMIT).any()
+            r = moemlp_cases.glu_f64(*moemlp_cases.split(pre), ALPHA, LIMIT)
+            got = h[listed].double().numpy()
+            ok, lo, hi = moemlp_cases.within_glu_bound(got, r, out_dtype)
+            worst = float((np.abs(got - r) / moemlp_cases.glu_tol(r)).max())
+            print(f"mx_grouped_glu random {nk} {ta} {routing}, x {x_dtype} -> {_name(out_dtype)}: worst |gpu - f64| / tol = {worst:.4f}"
+                  + (" (the output's own rounding included)" if out_dtype != torch.float32 else ""))
+            assert np.isfinite(got).all() and ok.all(), (nk, out_dtype, int((~ok).sum()), got[~ok][:4], lo[~ok][:4], hi[~ok][:4])
     # the down + sum form
     hrows = cases.random_rows(nk, ta, x_dtype, True)
     rw = torch.softmax(torch.randn(T, A, generator=torch.Generator().manual_seed(41300 + index)), dim=1).to(cases.DTYPES[index % 3])
@@ -261,14 +345,18 @@ def test_every_pair_has_the_bits_of_the_decode_launches(index):
 
 # ----------------------------------------------------------------------------- 4. the edges of the semantics
 def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only():
-    E, N, K, T, A = moe_cases.NAN_SHAPE
-    x64, w64, ids = moe_cases.nan_operands()
+    _nan_bytes(moe_cases.NAN_SHAPE, *moe_cases.nan_operands(), moe_cases.NAN_BLOCKS, moe_cases.NAN_BLOCKS[1])
+
+
+def _nan_bytes(shape, x64, w64, ids, blocks, forms_block):
+    """a 0xFF byte in each of `blocks` in turn (the plain form), and in `forms_block` for the GLU and the down + sum forms"""
+    E, N, K, T, A = shape
     w_codes, w_scales = cases.quantize_experts(w64)
     clean = _round_once(moe_cases.reference_f64(x64, w64, None, ids), torch.float32)
     hit = torch.zeros(T * A, N, dtype=torch.bool)
     hit[torch.from_numpy(ids.reshape(-1) == moe_cases.NAN_EXPERT), moe_cases.NAN_COLUMN] = True
     assert 0 < int(hit.sum()) < T * A
-    for i, b in enumerate(moe_cases.NAN_BLOCKS):
+    for i, b in enumerate(blocks):
         planted = w_scales.copy()
         planted[moe_cases.NAN_EXPERT, moe_cases.NAN_COLUMN, b] = 255
         for zero_x in (False, True):
@@ -281,7 +369,7 @@ def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only(
             _assert_bits(y[~hit], want[~hit], f"0xFF in block {b}, x block zero: {zero_x}: every other element")
     # the GLU and the down + sum forms: the output of that row, the tokens routed to that expert
     planted = w_scales.copy()
-    planted[moe_cases.NAN_EXPERT, moe_cases.NAN_COLUMN, moe_cases.NAN_BLOCKS[1]] = 255
+    planted[moe_cases.NAN_EXPERT, moe_cases.NAN_COLUMN, forms_block] = 255
     x = cases.to_dtype(x64, torch.bfloat16)
     h = run_grouped("glu", x, w_codes[:, :8], planted[:, :8], ids, None, torch.float32, FILLS[0])
     assert torch.equal(torch.isnan(h), hit[:, :8].reshape(T * A, 4, 2).any(dim=2))     # NaN exactly where a row of the output met the byte
@@ -295,13 +383,27 @@ def test_a_nan_scale_byte_makes_its_column_nan_for_the_pairs_of_its_expert_only(
 
 @pytest.mark.parametrize("x_dtype", cases.X16, ids=_name)
 def test_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
-    E, N, K, T, A = moe_cases.NAN_SHAPE
-    x64, w64, ids = moe_cases.nan_operands()
+    _bad_activations(moe_cases.NAN_SHAPE, *moe_cases.nan_operands(), moe_cases.X_BAD_KS, x_dtype)
+
+
+@pytest.mark.parametrize("K", cases.WALK_NONFINITE_KS)
+def test_nan_bytes_inf_and_nan_on_a_ragged_last_step_off_wave_0(K):
+    """The 0xFF byte on the first block of the last step and on block KB - 1 (all three forms see one of the two), the Inf and the NaN
+    at the first k of that step and at k = K - 1: the step runs on wave 7 (K = 992), on wave 6 in its third pass (K = 2880)"""
+    E, N, _, T, A = moe_cases.NAN_SHAPE
+    i = cases.WALK_NONFINITE_KS.index(K)
+    x64, w64, ids = moe_cases.walk_nan_operands(K)
+    _nan_bytes((E, N, K, T, A), x64, w64, ids, moe_cases.walk_nan_blocks(K), moe_cases.walk_nan_blocks(K)[i % 2])
+    _bad_activations((E, N, K, T, A), x64, w64, ids, moe_cases.walk_bad_ks(K), cases.X16[i % 2])
+
+
+def _bad_activations(shape, x64, w64, ids, ks, x_dtype):
+    E, N, K, T, A = shape
     w_codes, w_scales = cases.quantize_experts(w64)
     clean = _round_once(moe_cases.reference_f64(x64, w64, None, ids), torch.float32).reshape(T, A, N)
     other = torch.tensor([t != moe_cases.X_BAD_TOKEN for t in range(T)])
     n = 0
-    for ki, k in enumerate(moe_cases.X_BAD_KS):
+    for ki, k in enumerate(ks):
         for vi, v in enumerate(moe_cases.X_BAD_VALUES):
             xb = x64.copy()
             xb[moe_cases.X_BAD_TOKEN, k] = v
@@ -354,6 +456,78 @@ def test_ids_outside_the_experts_give_rows_of_plus_zero_and_leave_every_other_pa
             nan_rw = torch.full((T, A), float("nan"))
             for ws_fill in FILLS:                            # neither the routing weight nor the workspace row of a skipped pair is read
                 assert _is_plus_zero(run_grouped("down", hrows, w_codes, w_scales, every, None, od, FILLS[1], rw=nan_rw, ws_fill=ws_fill)), (v, od)
+
+
+# ----------------------------------------------------------------------------- 4b. past one column tile; many experts
+@pytest.mark.parametrize("index", range(len(cases.TILE_CASES)), ids=lambda i: "{}-N{}".format(*cases.TILE_CASES[i]))
+def test_glu_and_down_past_one_column_tile_against_float64_and_the_decode_launches(index):
+    """N on either side of the column tile and past two of them, counts on the row-tile edges, the four ids outside [0, E) among
+    them; the real alpha and limit.  GLU: the bits of mbnb_moemlp_gate_up_glu, inside within_glu_bound of the float64 chain over the
+    exact pre-activations, and rows of +0.0 across every column tile for the pairs outside.  Down + sum: the bits of float64 through
+    routed_sum_f32 (exact) and of mbnb_moemlp_down_sum, under both fills of the output and of the workspace"""
+    form, N = cases.TILE_CASES[index]
+    E, x_dtype = cases.TILE_E, cases.X16[index % 2]
+    rows64, w64, bias64, ids, rw64 = cases.tile_operands(form, N)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    rows, bias, rw = cases.to_dtype(rows64, x_dtype), cases.to_dtype(bias64, cases.DTYPES[index % 3]), cases.to_dtype(rw64, cases.DTYPES[(index + 1) % 3])
+    assert (bias.double().numpy() == bias64).all() and (rw.double().numpy() == rw64).all()
+    flat = ids.reshape(-1)
+    gone = torch.from_numpy((flat < 0) | (flat >= E))
+    assert int(gone.sum()) == 4
+    off = cases.OFFSETS[index % len(cases.OFFSETS)]
+    for out_dtype in (torch.float32, x_dtype):
+        if form == "glu":
+            pre = cases.reference("plain", rows64, w_codes, w_scales, ids, bias64).astype(np.float32)[~gone.numpy()]       # exact in f32
+            r = moemlp_cases.glu_f64(*moemlp_cases.split(pre), ALPHA, LIMIT)
+            want = yard_glu(rows, w_codes, w_scales, ids, bias, out_dtype)
+            for fill in FILLS:
+                h = run_grouped("glu", rows, w_codes, w_scales, ids, bias, out_dtype, fill, off)
+                _assert_bits(h, want, f"glu N = {N} -> {out_dtype}, fill {fill:#x}: against mbnb_moemlp_gate_up_glu")
+                assert _is_plus_zero(h[gone]) and h.shape[1] == N // 2
+                got = h[~gone].double().numpy()
+                ok, lo, hi = moemlp_cases.within_glu_bound(got, r, out_dtype)
+                assert np.isfinite(got).all() and ok.all(), (N, out_dtype, int((~ok).sum()), got[~ok][:4], lo[~ok][:4], hi[~ok][:4])
+        else:
+            want = _round_once(cases.reference("down", rows64, w_codes, w_scales, ids, bias64, rw=rw64).astype(np.float64), out_dtype)
+            _assert_bits(yard_down(rows, w_codes, w_scales, ids, bias, rw, out_dtype), want, f"down N = {N}: mbnb_moemlp_down_sum against float64")
+            for fill in FILLS:
+                for ws_fill in FILLS:
+                    out = run_grouped("down", rows, w_codes, w_scales, ids, bias, out_dtype, fill, off, rw=rw, ws_fill=ws_fill)
+                    _assert_bits(out, want, f"down N = {N} -> {out_dtype}, fill {fill:#x}, workspace {ws_fill:#x}")
+
+
+@pytest.mark.parametrize("form,N", cases.TILE_ALL_OUTSIDE, ids=lambda v: str(v))
+def test_every_id_outside_gives_plus_zero_across_every_column_tile_under_both_fills(form, N):
+    """No tile: every output element is written by the workgroups that leave, a column tile each; one that nobody wrote would keep
+    the fill under one of the two.  Down + sum: neither the routing weight nor the workspace row of a skipped pair is read"""
+    rows64, w64, bias64, ids, _ = cases.tile_operands("glu" if form == "glu" else "down", N)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    rows, bias = cases.to_dtype(rows64, torch.bfloat16), cases.to_dtype(bias64, torch.float32)
+    nan_rw = torch.full(ids.shape, float("nan"))
+    for i, v in enumerate(moe_cases.OUT_OF_RANGE):
+        every = np.full(ids.shape, np.int64(cases.TILE_E if v == moe_cases.IDS_SHAPE[0] else v).astype(np.int32), dtype=np.int32)
+        od = cases.DTYPES[i % 3]
+        for fill in FILLS:
+            for ws_fill in (FILLS if form == "down" else (None,)):
+                y = run_grouped(form, rows, w_codes, w_scales, every, bias, od, fill, cases.OFFSETS[i], rw=nan_rw, ws_fill=ws_fill)
+                assert _is_plus_zero(y) and y.shape[1] == (N // 2 if form == "glu" else N), (form, N, v, od, fill, ws_fill)
+
+
+@pytest.mark.parametrize("form", ("plain", "glu", "down"))
+@pytest.mark.parametrize("index", range(len(cases.MANY_CASES)), ids=lambda i: f"E{cases.MANY_CASES[i][0]}")
+def test_many_experts_bit_for_bit(index, form):
+    """E = 128 past one column tile and E = MAX_EXPERTS, sparse counts that include the lowest and the highest expert: float64
+    rounded once (the GLU form at alpha = 0, where its chain is exact)"""
+    case = cases.MANY_CASES[index]
+    rows64, w64, bias64, ids, rw64 = cases.many_operands(case, index, form)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    x_dtype, out_dtype = cases.X16[index % 2], cases.DTYPES[(index + len(form)) % 3]
+    rw = cases.to_dtype(rw64, torch.float32)
+    want = _round_once(np.asarray(cases.reference(form, rows64, w_codes, w_scales, ids, bias64, 0.0, LIMIT, rw64), dtype=np.float64), out_dtype)
+    for fill in FILLS:
+        y = run_grouped(form, cases.to_dtype(rows64, x_dtype), w_codes, w_scales, ids, cases.to_dtype(bias64, torch.float32), out_dtype, fill,
+                        cases.OFFSETS[(index + 1) % len(cases.OFFSETS)], alpha=0.0, limit=LIMIT, rw=rw)
+        _assert_bits(y, want, f"{form} {case[:5]}, fill {fill:#x}")
 
 
 # ----------------------------------------------------------------------------- 5. the Python surface

@@ -14,7 +14,7 @@ import torch
 import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _moe_native as moen, _moemlp_native as mlpn, _native
 from mps_bitsandbytes_amd._native import ptr, stream_ptr
-from tests import guard, moemlp_cases as cases, mx_emul as emul
+from tests import guard, moe_cases, moemlp_cases as cases, mx_emul as emul
 from tests.test_gpu_mx import _assert_bits, _round_once
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +148,30 @@ def test_glu_with_alpha_zero_bit_for_bit(index):
         _assert_bits(h, want, f"glu alpha 0 {case[:5]}, fill {fill:#x}")
 
 
+def _pre_is_float64(pre, x64, w_codes, w_scales, bias64, ids):
+    """the yardstick's f32 pre-activations are the float64 result over the decoded weights, rounded once"""
+    want = _round_once(moe_cases.reference_f64(x64, moe_cases.decode_experts(w_codes, w_scales), bias64, ids), torch.float32)
+    _assert_bits_nan(torch.from_numpy(pre), want, "the f32 pre-activations against float64")
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_GLU_CASES)), ids=lambda i: f"K{cases.WALK_KS[i]}")
+def test_glu_with_alpha_zero_at_every_k_of_the_walk_bit_for_bit(index):
+    """tests/moe_cases.py WALK_KS through k_mx_experts_rt's GLU epilogue, under the rule of test_glu_with_alpha_zero_bit_for_bit"""
+    case = cases.WALK_GLU_CASES[index]
+    E, I, K, T, A, _, x_dtype, out_dtype, _, limit = case
+    x64, w64, bias64, ids = cases.glu_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    x = cases.to_dtype(x64, x_dtype)
+    bias = None if bias64 is None else cases.to_dtype(bias64, cases.DTYPES[(index + 1) % 3])
+    pre = run_parent(x, w_codes, w_scales, ids, bias)
+    assert np.isfinite(pre).all()
+    _pre_is_float64(pre, x64, w_codes, w_scales, bias64, ids)
+    want = _glu_want(pre, 0.0, limit, out_dtype)
+    for fill in FILLS:
+        h = run_glu(x, w_codes, w_scales, ids, bias, 0.0, limit, out_dtype, fill, cases.OFFSETS[index % len(cases.OFFSETS)])
+        _assert_bits(h, want, f"glu alpha 0 at K = {K} {case[:5]}, fill {fill:#x}")
+
+
 # ----------------------------------------------------------------------------- 2. alpha = 1.702 against float64
 def _assert_glu_bound(h, pre, out_dtype, what):
     g, u = cases.split(pre)
@@ -216,8 +240,8 @@ def test_glu_on_random_data_inside_the_bound_and_every_pair_alone_and_in_another
 
 
 # ----------------------------------------------------------------------------- 4. the edges of the semantics
-def _edge_glu_operands():
-    E, I, K, T, A = cases.EDGE_SHAPE
+def _edge_glu_operands(K=cases.EDGE_SHAPE[2]):
+    E, I, _, T, A = cases.EDGE_SHAPE
     x64 = emul.lossless(T, K, seed=39501) * 0.125
     w64 = emul.lossless(E * 2 * I, K, seed=39502).reshape(E, 2 * I, K)
     bias = torch.from_numpy(np.random.default_rng(39503).integers(1, 9, size=(E, 2 * I)).astype(F32))      # never zero: a bias that leaked shows
@@ -246,15 +270,14 @@ def test_glu_ids_outside_the_experts_give_rows_of_plus_zero_and_leave_every_othe
                 assert _is_plus_zero(run_glu(x, w_codes, w_scales, every, bias, cases.ALPHA, cases.LIMIT, od, fill)), (v, od, fill)
 
 
-@pytest.mark.parametrize("row", (0, 1), ids=("gate-row", "up-row"))
-def test_glu_a_nan_scale_byte_makes_its_output_nan_for_the_pairs_of_its_expert_only(row):
-    E, I, K, T, A = cases.EDGE_SHAPE
-    x64, (w_codes, w_scales), bias, ids = _edge_glu_operands()
+def _glu_nan_bytes(row, K, blocks):
+    E, I, _, T, A = cases.EDGE_SHAPE
+    x64, (w_codes, w_scales), bias, ids = _edge_glu_operands(K)
     clean = None
     hit = torch.zeros(T * A, I, dtype=torch.bool)
     hit[torch.from_numpy(ids.reshape(-1) == cases.NAN_EXPERT), cases.NAN_OUTPUT] = True
     assert 0 < int(hit.sum()) < T * A
-    for i, b in enumerate(cases.NAN_BLOCKS):
+    for i, b in enumerate(blocks):
         x = cases.to_dtype(x64, cases.X16[i % 2])
         clean = run_glu(x, w_codes, w_scales, ids, bias, cases.ALPHA, cases.LIMIT, torch.float32, FILLS[0])
         assert bool(torch.isfinite(clean).all())
@@ -266,14 +289,18 @@ def test_glu_a_nan_scale_byte_makes_its_output_nan_for_the_pairs_of_its_expert_o
             _assert_bits(h[~hit], clean[~hit], f"0xFF in block {b} of the {('gate', 'up')[row]} row: every other element")
 
 
-@pytest.mark.parametrize("x_dtype", cases.X16, ids=_name)
-def test_glu_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
-    E, I, K, T, A = cases.EDGE_SHAPE
-    x64, (w_codes, w_scales), bias, ids = _edge_glu_operands()
+@pytest.mark.parametrize("row", (0, 1), ids=("gate-row", "up-row"))
+def test_glu_a_nan_scale_byte_makes_its_output_nan_for_the_pairs_of_its_expert_only(row):
+    _glu_nan_bytes(row, cases.EDGE_SHAPE[2], cases.NAN_BLOCKS)
+
+
+def _glu_bad_activations(x_dtype, K, ks):
+    E, I, _, T, A = cases.EDGE_SHAPE
+    x64, (w_codes, w_scales), bias, ids = _edge_glu_operands(K)
     clean = run_glu(cases.to_dtype(x64, x_dtype), w_codes, w_scales, ids, bias, cases.ALPHA, cases.LIMIT, torch.float32, FILLS[0]).reshape(T, A, I)
     other = torch.tensor([t != cases.X_BAD_TOKEN for t in range(T)])
     seen_nan = 0
-    for ki, k in enumerate((0, 31, 32, K - 1)):
+    for ki, k in enumerate(ks):
         for vi, v in enumerate(cases.X_BAD_VALUES):
             xb = x64.copy()
             xb[cases.X_BAD_TOKEN, k] = v
@@ -286,6 +313,21 @@ def test_glu_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
             _assert_bits(h[other], clean[other], f"{v} at k = {k}: the other tokens")
             seen_nan += int(torch.isnan(h[cases.X_BAD_TOKEN]).sum())
     assert seen_nan > 0
+
+
+@pytest.mark.parametrize("x_dtype", cases.X16, ids=_name)
+def test_glu_inf_and_nan_in_a_token_row_touch_that_tokens_pairs_only(x_dtype):
+    K = cases.EDGE_SHAPE[2]
+    _glu_bad_activations(x_dtype, K, (0, 31, 32, K - 1))
+
+
+@pytest.mark.parametrize("K", cases.WALK_NONFINITE_KS)
+def test_glu_nan_bytes_inf_and_nan_on_a_ragged_last_step_off_wave_0(K):
+    """The 0xFF byte on the first block of the last step and on block KB - 1 (of a gate row at one K, of an up row at the other), the
+    Inf and the NaN at the first k of that step and at k = K - 1: the step runs on wave 7 (K = 992), on wave 6 in its third pass (2880)"""
+    i = cases.WALK_NONFINITE_KS.index(K)
+    _glu_nan_bytes(i % 2, K, moe_cases.walk_nan_blocks(K))
+    _glu_bad_activations(cases.X16[i % 2], K, moe_cases.walk_bad_ks(K))
 
 
 # ----------------------------------------------------------------------------- 5. down + sum, bit for bit
@@ -304,6 +346,25 @@ def test_down_and_routed_sum_bit_for_bit(index):
     for fill in FILLS:
         out = run_down(h, w_codes, w_scales, ids, bias, rw, out_dtype, fill, cases.OFFSETS[index % len(cases.OFFSETS)])
         _assert_bits_nan(out, want, f"down + sum {case[:5]}, fill {fill:#x}")
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_SUM_CASES)), ids=lambda i: f"K{cases.WALK_KS[i]}")
+def test_down_and_routed_sum_at_every_k_of_the_walk_bit_for_bit(index):
+    """tests/moe_cases.py WALK_KS through k_mx_experts_rt's f32 epilogue and k_routed_sum, under the rule of the test above"""
+    case = cases.WALK_SUM_CASES[index]
+    E, N, K, T, A, _, h_dtype, out_dtype, _, rw_dtype = case
+    h64, w64, bias64, ids, rw64 = cases.sum_operands(case, cases.WALK_SEED + index)
+    w_codes, w_scales = cases.quantize_experts(w64)
+    h = cases.to_dtype(h64, h_dtype)
+    rw = cases.to_dtype(rw64, rw_dtype)
+    assert (rw.double().numpy() == rw64).all()
+    bias = None if bias64 is None else cases.to_dtype(bias64, cases.DTYPES[(index + 1) % 3])
+    y = run_parent(h, w_codes, w_scales, ids, bias)
+    _pre_is_float64(y, h64, w_codes, w_scales, bias64, ids)
+    want = _sum_want(y, rw, ids, E, out_dtype)
+    for fill in FILLS:
+        out = run_down(h, w_codes, w_scales, ids, bias, rw, out_dtype, fill, cases.OFFSETS[index % len(cases.OFFSETS)])
+        _assert_bits_nan(out, want, f"down + sum at K = {K} {case[:5]}, fill {fill:#x}")
 
 
 @pytest.mark.parametrize("h_dtype", cases.X16, ids=_name)
@@ -325,8 +386,8 @@ def test_down_and_routed_sum_on_random_data_bit_for_bit(h_dtype):
 
 
 # ----------------------------------------------------------------------------- 6. skipping, NaN bytes, the workspace
-def _edge_sum_operands():
-    E, N, K, T, A = cases.EDGE_SHAPE
+def _edge_sum_operands(K=cases.EDGE_SHAPE[2]):
+    E, N, _, T, A = cases.EDGE_SHAPE
     h64 = (emul.lossless(T * A, K, seed=39701) * 0.125).reshape(T, A, K)
     w64 = emul.lossless(E * N, K, seed=39702).reshape(E, N, K)
     bias = torch.from_numpy(np.random.default_rng(39703).integers(1, 9, size=(E, N)).astype(F32))
@@ -360,20 +421,29 @@ def test_sum_skips_ids_outside_the_experts_without_reading_their_routing_weight_
             assert _is_plus_zero(run_down(h, w_codes, w_scales, every, bias, rwp, torch.bfloat16, fill)), (v, fill)
 
 
-def test_sum_a_nan_scale_byte_makes_its_column_nan_for_the_tokens_routed_to_its_expert_only():
-    E, N, K, T, A = cases.EDGE_SHAPE
-    h, (w_codes, w_scales), bias, ids, rw = _edge_sum_operands()
+def _sum_nan_bytes(K, blocks):
+    E, N, _, T, A = cases.EDGE_SHAPE
+    h, (w_codes, w_scales), bias, ids, rw = _edge_sum_operands(K)
     hit = torch.zeros(T, N, dtype=torch.bool)
     hit[torch.from_numpy((ids == cases.NAN_EXPERT).any(axis=1)), cases.NAN_OUTPUT] = True
     assert 0 < int(hit[:, cases.NAN_OUTPUT].sum()) < T
     clean = run_down(h, w_codes, w_scales, ids, bias, rw, torch.float32, FILLS[0])
     assert bool(torch.isfinite(clean).all())
-    for i, b in enumerate(cases.NAN_BLOCKS):
+    for i, b in enumerate(blocks):
         planted = w_scales.copy()
         planted[cases.NAN_EXPERT, cases.NAN_OUTPUT, b] = 255
         out = run_down(h, w_codes, planted, ids, bias, rw, torch.float32, FILLS[i % 2], cases.OFFSETS[1 + i])
         assert bool(torch.isnan(out[hit]).all()), b
         _assert_bits(out[~hit], clean[~hit], f"0xFF in block {b}: every other element")
+
+
+def test_sum_a_nan_scale_byte_makes_its_column_nan_for_the_tokens_routed_to_its_expert_only():
+    _sum_nan_bytes(cases.EDGE_SHAPE[2], cases.NAN_BLOCKS)
+
+
+@pytest.mark.parametrize("K", cases.WALK_NONFINITE_KS)
+def test_sum_a_nan_scale_byte_on_a_ragged_last_step_off_wave_0(K):
+    _sum_nan_bytes(K, moe_cases.walk_nan_blocks(K))
 
 
 # ----------------------------------------------------------------------------- 7. the Python surface

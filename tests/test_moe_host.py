@@ -275,9 +275,11 @@ def _normal_or_zero(a):
 def test_every_exact_case_is_exact_in_f32_in_any_order(index):
     """Every row of the call against every row of every expert (a superset of the routed pairs): the sum of the product
     magnitudes of an output, and of a block, is below 2^24 units of its product grid; operands, partial sums and results are normal."""
-    case = cases.EXACT_CASES[index]
+    _assert_exact_in_any_order(cases.EXACT_CASES[index], *cases.exact_operands(cases.EXACT_CASES[index], index))
+
+
+def _assert_exact_in_any_order(case, x, w, bias, ids):
     E, N, K, T, A, counts, x_dtype, _, _, per_slot = case
-    x, w, bias, ids = cases.exact_operands(case, index)
     assert x.shape == ((T, A, K) if per_slot else (T, K)) and ids.shape == (T, A) and ids.dtype == np.int32
     assert np.bincount(ids.reshape(-1), minlength=E).tolist() == list(counts) and len(counts) == E and T * A <= cases.MAX_PAIRS
     rows = x.reshape(-1, K)
@@ -313,6 +315,56 @@ def test_the_exact_cases_cover_every_listed_size():
     assert any(c[0] == 1 and c[4] > 1 for c in cases.EXACT_CASES)                            # the same expert twice within a token
     assert cases.launch_text(torch.bfloat16, False, 32, 64) == "mx_experts bf16 shared E32 P64"
     assert cases.launch_text(torch.float16, True, 4, 5) == "mx_experts f16 slot E4 P5"
+
+
+def test_the_walk_table_has_the_steps_tails_waves_and_passes_it_names():
+    """From K by formula: step c of ceil(KB / 4) runs on wave c % 8 in pass c // 8; the last step holds KB - 4 (steps - 1) blocks"""
+    want = {352: (3, 3, 2, 0), 448: (4, 2, 3, 0), 992: (8, 3, 7, 0), 1024: (8, 4, 7, 0), 1216: (10, 2, 1, 1), 2016: (16, 3, 7, 1),
+            2048: (16, 4, 7, 1), 2880: (23, 2, 6, 2), 3104: (25, 1, 0, 3)}
+    assert tuple(want) == cases.WALK_KS
+    walks = {}
+    for K in cases.WALK_KS:
+        assert K % 32 == 0
+        KB = K // 32
+        steps = (KB + 3) // 4                                # csrc/mx_decode.h tile_walk, csrc/moegemm_kernels.hip
+        owner = [c % 8 for c in range(steps)]
+        tail = sum(1 for q in range(4) if 4 * (steps - 1) + q < KB)
+        walks[K] = (steps, tail, owner[-1], sum(1 for c in range(steps - 1) if c % 8 == owner[-1]))
+        got = cases.walk_of(K)
+        assert (got["steps"], got["tail"], got["wave"], got["passes"]) == walks[K] == want[K], K
+        assert got["first"] == 4 * (steps - 1) and cases.walk_nan_blocks(K) == tuple(sorted({got["first"], KB - 1}))
+        assert cases.walk_bad_ks(K) == (128 * (steps - 1), K - 1)
+    assert {w[1] for w in walks.values()} == {1, 2, 3, 4}
+    ragged = {w[2] for w in walks.values() if w[1] < 4}
+    assert 0 in ragged and 7 in ragged and ragged & set(range(1, 7))
+    assert {w[3] for w in walks.values()} == {0, 1, 2, 3}
+    assert {K for K in cases.WALK_KS if K % cases.ROUND == 0} == {1024, 2048} and 2880 in cases.WALK_KS
+    assert any(w[0] >= 25 for w in walks.values())            # tile_walk's second outer iteration has a live u = 1 step from 25 steps on
+    assert not set(cases.WALK_KS) & {c[2] for c in cases.EXACT_CASES}
+    # what the older table leaves out, by the same formula: ragged steps on waves 0 and 1 only, of 2 or 3 blocks only alone on wave 0
+    old = {K: cases.walk_of(K) for K in sorted({c[2] for c in cases.EXACT_CASES})}
+    assert {w["wave"] for w in old.values() if w["tail"] < 4} == {0, 1} and {w["tail"] for w in old.values() if w["steps"] > 1} == {1}
+    assert max(w["passes"] for w in old.values()) == 2
+    assert set(cases.WALK_NONFINITE_KS) <= set(cases.WALK_KS) and all(cases.walk_of(K)["wave"] != 0 and cases.walk_of(K)["tail"] < 4 for K in cases.WALK_NONFINITE_KS)
+    assert all(len(cases.walk_nan_blocks(K)) == 2 for K in cases.WALK_NONFINITE_KS)
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_CASES)))
+def test_every_walk_case_is_exact_in_f32_in_any_order(index):
+    case = cases.WALK_CASES[index]
+    assert case[:6] == (3, 17, cases.WALK_KS[index], 11, 3, (17, 0, 16)) and case[1] == cases.TILE + 1
+    assert 3104 * 144 / 2.0 ** -4 < 2.0 ** 24                 # the worst case of lossless rows at the longest K
+    _assert_exact_in_any_order(case, *cases.exact_operands(case, cases.WALK_SEED + index))
+
+
+def test_the_walk_cases_alternate_every_form():
+    W = cases.WALK_CASES
+    assert [c[2] for c in W] == list(cases.WALK_KS)
+    assert {c[6] for c in W} == set(cases.X16) and {c[7] for c in W} == set(cases.DTYPES) and {c[8] for c in W} == {True, False} == {c[9] for c in W}
+    assert all(W[i][6] != W[i + 1][6] and W[i][7] != W[i + 1][7] for i in range(len(W) - 1))
+    for K in cases.WALK_NONFINITE_KS:                        # the planted column and expert have a weight at both planted k
+        x, w, ids = cases.walk_nan_operands(K)
+        assert x.shape == (cases.NAN_SHAPE[3], K) and w.shape == (3, cases.NAN_SHAPE[1], K) and (np.abs(x) @ np.abs(w.reshape(-1, K)).T).max() < 2.0 ** 20
 
 
 @pytest.mark.parametrize("which", ("low", "high"))

@@ -16,7 +16,7 @@ import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _moe_native as moen, _moegemm_native as gn, _moemlp_native as mlpn, _mx_native as mxn, _router_native as rn
 from mps_bitsandbytes_amd import functional as F
 from tests import moegemm_cases as cases
-from tests.test_moe_host import _normal_or_zero, _walk
+from tests.test_moe_host import _assert_exact_in_any_order, _normal_or_zero, _walk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mbnb_moegemm.h")
@@ -431,3 +431,202 @@ def test_the_case_tables_cover_every_listed_size():
     T, A, E, H, I = cases.ROUTE_SHAPE
     assert T * A >= 2048 and T * A > mlpn.MAX_PAIRS
     assert cases.experts_text(torch.bfloat16, False, 32, 4096) == "mx_grouped bf16 shared E32 P4096 R64"
+
+
+# ----------------------------------------------------------------------------- the K walk and the column tiles
+def test_the_walk_and_tile_tables_cover_what_they_name():
+    C, R = cases.C, cases.R
+    assert cases.WALK_KS is cases.moe_cases.WALK_KS and not set(cases.WALK_KS) & {c[2] for c in cases.EXACT_CASES}
+    for table, n in ((cases.WALK_CASES, C + 1), (cases.WALK_GLU_CASES, C // 2 + 1), (cases.WALK_SUM_CASES, C + 1)):
+        assert [c[2] for c in table] == list(cases.WALK_KS) and all(c[:2] == (3, n) and c[3:6] == (17, 4, (R + 1, 0, 3)) for c in table)
+        assert {c[6] for c in table} == set(cases.X16) and {c[7] for c in table} == set(cases.DTYPES) and {c[8] for c in table} == {True, False}
+        assert all(table[i][6] != table[i + 1][6] and table[i][7] != table[i + 1][7] for i in range(len(table) - 1))
+    assert {c[9] for c in cases.WALK_CASES} == {True, False} and {c[9] for c in cases.WALK_SUM_CASES} == set(cases.DTYPES)
+    assert {c[9] for c in cases.WALK_GLU_CASES} == {cases.moemlp_cases.LIMIT, INF}
+    plan = cases.plan_reference(cases.exact_operands(cases.WALK_CASES[0], cases.WALK_SEED)[3], 3)
+    assert plan["tiles"][:, 0].tolist() == [0, 0, 2] and plan["tiles"][:, 2].tolist() == [R, 1, 3]       # a full tile, a one-row tile
+    assert cases.WALK_RANDOM_WEIGHTS == ((17, 2880), (C + 1, 992)) and cases.WALK_RANDOM_PAIRS == (35, 2)
+    assert not set(cases.WALK_RANDOM_WEIGHTS) & set(cases.RANDOM_WEIGHTS)
+    assert cases.TILE_CASES == [("glu", C - 2), ("glu", C), ("glu", C + 2), ("glu", 2 * C + 2), ("down", C - 1), ("down", C), ("down", C + 1), ("down", 2 * C + 1)]
+    assert [n // 2 for f, n in cases.TILE_CASES if f == "glu"] == [23, 24, 25, 49] and cases.TILE_K == 160
+    ids = cases.tile_ids()
+    flat = ids.reshape(-1).astype(np.int64)
+    assert ids.shape == (cases.TILE_T, cases.TILE_A) and ids.dtype == np.int32
+    assert np.bincount(flat[(flat >= 0) & (flat < cases.TILE_E)], minlength=cases.TILE_E).tolist()[:5] == [0, 1, R - 1, R, R + 1]
+    assert sorted(flat[(flat < 0) | (flat >= cases.TILE_E)].tolist()) == [-2 ** 31, -1, cases.TILE_E, 2 ** 31 - 1]
+    assert cases.TILE_ALL_OUTSIDE == (("glu", 2 * C + 2), ("plain", 2 * C + 1), ("down", 2 * C + 1))
+    (E1, N1, K1, T1, A1, c1), (E2, N2, K2, T2, A2, c2) = cases.MANY_CASES
+    assert (E1, N1, K1) == (128, C + 1, 64) and (E2, N2, K2) == (gn.MAX_EXPERTS, 1, 32) == (mlpn.MAX_EXPERTS, 1, 32)
+    for (E, N, K, T, A, counts) in cases.MANY_CASES:
+        assert len(counts) == E and sum(counts) == T * A and counts[0] and counts[-1] and sum(1 for c in counts if c) < 8
+    assert E1 * (C + 1) * 32 == 128 * 49 * 32                  # the largest weight of these tables, in bytes
+
+
+def _close(rows, x_dtype, w, bias, ids, unit):
+    """rows exact in their 16-bit type, weights that quantise to their own codes, every block's partial sum a multiple of the unit,
+    the sum of the magnitudes below 2^24 units: every order of the f32 sums gives the float64 result"""
+    E, N, K = w.shape
+    flat = rows.reshape(-1, K)
+    assert (cases.to_dtype(flat, x_dtype).double().numpy() == flat).all()
+    codes, scales = cases.quantize_experts(w)
+    assert (cases.moe_cases.decode_experts(codes, scales) == w).all()
+    w2 = w.reshape(E * N, K)
+    total = np.abs(flat) @ np.abs(w2).T + (0 if bias is None else np.abs(bias).reshape(-1)[None, :])
+    assert total.max() / unit < 2.0 ** 24, total.max()
+    blocks = np.einsum("mbk,nbk->mnb", flat.reshape(flat.shape[0], -1, 32), w2.reshape(E * N, -1, 32))
+    assert (blocks % unit == 0).all() and _normal_or_zero(blocks) and (blocks.sum(axis=2) == flat @ w2.T).all()
+    pre = cases.moe_cases.reference_f64(rows, w, bias, ids)
+    assert (pre % unit == 0).all() and (pre.astype(np.float32) == pre).all()
+    return pre
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_KS)))
+def test_every_walk_case_of_the_three_forms_is_exact_in_f32_in_any_order(index):
+    assert 3104 * 144 / 2.0 ** -4 < 2.0 ** 24                 # the worst case of lossless rows at the longest K
+    case = cases.WALK_CASES[index]
+    x, w, bias, ids = cases.exact_operands(case, cases.WALK_SEED + index)
+    _assert_exact_in_any_order(case, x, w, bias, ids)
+    case = cases.WALK_GLU_CASES[index]
+    x, w, bias, ids = cases.glu_operands(case, cases.WALK_SEED + index)
+    pre = _close(x, case[6], w, bias, ids, 2.0 ** -7)
+    assert w.shape[1] == cases.C + 2 and (np.abs(pre) < 7.0).any() and (pre > 7.0).any() and (pre < -7.0).any()
+    case = cases.WALK_SUM_CASES[index]
+    h, w, bias, ids, rw = cases.sum_operands(case, cases.WALK_SEED + index)
+    _close(h, case[6], w, bias, ids, 2.0 ** -7)
+    for dtype in cases.DTYPES:
+        assert (cases.to_dtype(rw, dtype).double().numpy() == rw).all()
+
+
+def test_the_tile_and_many_expert_cases_are_exact_in_f32_in_any_order():
+    for form, N in cases.TILE_CASES:
+        rows, w, bias, ids, rw = cases.tile_operands(form, N)
+        inside = np.where((ids >= 0) & (ids < cases.TILE_E), ids, 0)
+        pre = _close(rows, torch.float16, w, bias, inside, 2.0 ** -7)
+        _close(rows, torch.bfloat16, w, bias, inside, 2.0 ** -7)
+        assert (bias != 0).all() and w.shape == (cases.TILE_E, N, cases.TILE_K)
+        if form == "glu":
+            assert (np.abs(pre) < 7.0).any() and (pre > 7.0).any() and (pre < -7.0).any()
+    for index, case in enumerate(cases.MANY_CASES):
+        for form in ("plain", "glu", "down"):
+            rows, w, bias, ids, rw = cases.many_operands(case, index, form)
+            _close(rows, torch.bfloat16, w, bias, ids, 2.0 ** -7)
+            assert w.shape[1] == case[1] + (form == "glu") and np.bincount(ids.reshape(-1), minlength=case[0]).tolist() == list(case[5])
+
+
+# ----------------------------------------------------------------------------- the kernel restated, and the mistakes the tables are for
+def _call(form, rows, w, bias, ids, rw=None, alpha=0.0, limit=INF, scales=None):
+    codes, s = cases.quantize_experts(w)
+    return dict(form=form, x=rows, codes=codes, scales=s if scales is None else scales, ids=ids, bias=bias, rw=rw, alpha=alpha, limit=limit)
+
+
+def _planted(ids, E):
+    out = ids.copy()
+    for (t, a), v in zip(cases.moe_cases.OUT_OF_RANGE_PLACES, cases.moe_cases.OUT_OF_RANGE):
+        out[t, a] = np.int64(E if v == cases.moe_cases.IDS_SHAPE[0] else v).astype(np.int32)
+    return out
+
+
+def _nonfinite_calls(x, w, ids, blocks, bad_ks):
+    """the bodies of the 0xFF, Inf and NaN tests of tests/test_gpu_moegemm.py as calls: one planted byte or value each"""
+    mc = cases.moe_cases
+    _, scales = cases.quantize_experts(w)
+    out = []
+    for b in blocks:
+        planted = scales.copy()
+        planted[mc.NAN_EXPERT, mc.NAN_COLUMN, b] = 255
+        out.append(_call("plain", x, w, None, ids, scales=planted))
+    for k in bad_ks:
+        for v in mc.X_BAD_VALUES:
+            xb = x.copy()
+            xb[mc.X_BAD_TOKEN, k] = v
+            out.append(_call("plain", xb, w, None, ids))
+    return out
+
+
+def _old_tables():
+    """What the suite held before the walk and tile tables: EXACT_CASES (plain), the non-finite edges at K = 160, and the shapes at
+    which the GLU and the down + sum forms ran (the bit rule's N = 16 and 32, 17 and 33; the edge tests' 16, 8 and 9, with the
+    out-of-range ids), here on lossless operands"""
+    mc, ml = cases.moe_cases, cases.moemlp_cases
+    tables = {"EXACT_CASES": [_call("plain", *cases.exact_operands(c, i)) for i, c in enumerate(cases.EXACT_CASES)]}
+    x, w, ids = mc.nan_operands()
+    tables["non-finite, K = 160"] = _nonfinite_calls(x, w, ids, mc.NAN_BLOCKS, mc.X_BAD_KS)
+    forms = []
+    for i, (N, K) in enumerate(cases.RANDOM_WEIGHTS):
+        T, A = cases.RANDOM_PAIRS[0]
+        ids = cases.random_routing((T, A), "uniform")
+        w = ml.emul.lossless(cases.RANDOM_E * N, K, seed=46000 + i).reshape(cases.RANDOM_E, N, K)
+        bias = np.random.default_rng(46100 + i).integers(1, 9, size=(cases.RANDOM_E, N)).astype(np.float64)
+        rw = np.random.default_rng(46200 + i).integers(1, 33, size=(T, A)) / 64.0
+        forms.append(_call("glu", ml.emul.lossless(T, K, seed=46300 + i) * 0.125, w[:, :N - N % 2], bias[:, :N - N % 2], ids))
+        forms.append(_call("down", (ml.emul.lossless(T * A, K, seed=46400 + i) * 0.125).reshape(T, A, K), w, bias, ids, rw))
+    E, N, K, T, A = mc.IDS_SHAPE
+    x, w, bias, ids = mc.ids_operands()
+    rw = np.random.default_rng(46500).integers(1, 33, size=(T, A)) / 64.0
+    h = np.repeat(x[:, None, :], A, axis=1)
+    for planted in (_planted(ids, E), np.full((T, A), -1, dtype=np.int32)):
+        forms += [_call("plain", x, w, bias, planted), _call("glu", x, w[:, :16], bias[:, :16], planted), _call("down", h, w, bias, planted, rw)]
+    x, w, ids = mc.nan_operands()
+    forms += [_call("glu", x, w[:, :8], None, ids), _call("down", np.repeat(x[:, None, :], ids.shape[1], axis=1), w, None, ids, np.ones(ids.shape))]
+    tables["GLU and down, one column tile"] = forms
+    return tables
+
+
+def _new_tables():
+    mc = cases.moe_cases
+    tables = {"WALK_CASES": [_call("plain", *cases.exact_operands(c, cases.WALK_SEED + i)) for i, c in enumerate(cases.WALK_CASES)],
+              "WALK_GLU_CASES": [_call("glu", *cases.glu_operands(c, cases.WALK_SEED + i), limit=c[9]) for i, c in enumerate(cases.WALK_GLU_CASES)],
+              "WALK_SUM_CASES": [_call("down", *cases.sum_operands(c, cases.WALK_SEED + i)) for i, c in enumerate(cases.WALK_SUM_CASES)]}
+    tables["non-finite on the walk's tails"] = [call for K in cases.WALK_NONFINITE_KS
+                                                for call in _nonfinite_calls(*mc.walk_nan_operands(K), mc.walk_nan_blocks(K), mc.walk_bad_ks(K))]
+    tiles = []
+    for form, N in cases.TILE_CASES:
+        rows, w, bias, ids, rw = cases.tile_operands(form, N)
+        tiles.append(_call(form, rows, w, bias, ids, rw, alpha=0.0, limit=cases.moemlp_cases.LIMIT))
+    tables["TILE_CASES"] = tiles
+    outside = []
+    for form, N in cases.TILE_ALL_OUTSIDE:
+        rows, w, bias, ids, rw = cases.tile_operands("glu" if form == "glu" else "down", N)
+        outside.append(_call(form, rows, w, bias, np.full(ids.shape, -1, dtype=np.int32), rw))
+    tables["TILE_ALL_OUTSIDE"] = outside
+    tables["MANY_CASES"] = [_call(form, *cases.many_operands(c, i, form)) for i, c in enumerate(cases.MANY_CASES) for form in ("plain", "glu", "down")]
+    return tables
+
+
+def _restated(call, mutate=None):
+    return cases.grouped_as_kernel(call["x"], call["codes"], call["scales"], call["ids"], call["bias"], call["form"], mutate, call["alpha"], call["limit"], call["rw"])
+
+
+def test_the_restated_kernel_is_the_float64_reference_and_the_new_tables_catch_what_the_old_ones_let_through():
+    """grouped_as_kernel, unmutated, equals the float64 reference on every exact table, old and new.  Then every mutation on every
+    table: which tables see it.  Written down (the matrix is printed):
+      - the new tables catch every mutation that changes a result;
+      - "tail_keeps_w" changes none: the activation of a block past K is zeroed too, so its products are 0 whatever the weight
+        registers hold, and the two zeroings of the kernel guard each other.  No table can catch it; it is asserted to be silent;
+      - "steps_floor" and "tail_only_wave_idle" were caught before (K = 32 to 96 are one ragged step on wave 0, K = 160 a ragged
+        step alone on wave 1); "tail_past_wave_1" and "three_passes" are what the old K set really left open: a ragged step on
+        waves 2 to 7, and a fourth pass;
+      - "tail_keeps_x_and_scale" shows only through a non-finite activation in the clamped block (Inf x 0), at k = K - 1: the old
+        K = 160 edge saw it on wave 1, the new ones see it on waves 6 and 7;
+      - the three epilogue mutations and the two above pass every old table."""
+    old, new = _old_tables(), _new_tables()
+    wants = {}
+    for name, table in {**old, **new}.items():
+        wants[name] = []
+        for call in table:
+            want = cases.reference(call["form"], call["x"], call["codes"], call["scales"], call["ids"], call["bias"], call["alpha"], call["limit"], call["rw"])
+            assert cases.same_values(_restated(call), want), (name, call["form"], call["codes"].shape)
+            wants[name].append(want)
+    matrix = {m: {name: any(not cases.same_values(_restated(call, m), want) for call, want in zip(table, wants[name]))
+                  for name, table in {**old, **new}.items()} for m in cases.MUTANTS}
+    for m in cases.MUTANTS:
+        print(f"mutation {m}: caught by " + (", ".join(name for name, hit in matrix[m].items() if hit) or "no table"))
+    by_old = {m for m in cases.MUTANTS if any(matrix[m][name] for name in old)}
+    by_new = {m for m in cases.MUTANTS if any(matrix[m][name] for name in new)}
+    assert by_new == set(cases.MUTANTS) - {"tail_keeps_w"} and "tail_keeps_w" not in by_old
+    assert by_old == {"steps_floor", "tail_only_wave_idle", "tail_keeps_x_and_scale"}
+    assert not by_old & {"glu_column_forgets_n0", "zeros_on_column_tile_0", "workspace_stride_of_a_tile", "tail_past_wave_1", "three_passes"}
+    exact_new = [name for name in new if name != "non-finite on the walk's tails"]
+    assert all(any(matrix[m][name] for name in exact_new) for m in by_new - {"tail_keeps_x_and_scale"})
+    assert matrix["three_passes"]["WALK_CASES"] and matrix["tail_past_wave_1"]["WALK_GLU_CASES"] and matrix["workspace_stride_of_a_tile"]["WALK_SUM_CASES"]
+    assert matrix["glu_column_forgets_n0"]["TILE_CASES"] and matrix["zeros_on_column_tile_0"]["TILE_CASES"] and matrix["zeros_on_column_tile_0"]["TILE_ALL_OUTSIDE"]

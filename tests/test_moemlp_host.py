@@ -13,7 +13,7 @@ import torch
 
 import mps_bitsandbytes_amd as bnb
 from mps_bitsandbytes_amd import _moe_native as moen, _moemlp_native as mlpn, _mx_native as mxn
-from tests import moemlp_cases as cases, optim_emul
+from tests import moe_cases, moemlp_cases as cases, optim_emul
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mbnb_moemlp.h")
@@ -429,3 +429,50 @@ def test_the_case_tables_cover_every_listed_size():
     T, A, E, I, H = cases.CUT_SHAPE
     assert T * A > cases.MAX_PAIRS and (cases.MAX_PAIRS // A) * 2 > T > cases.MAX_PAIRS // A
     assert cases.glu_text(torch.bfloat16, 32, 4) == "mx_glu bf16 E32 P4 R4" and cases.down_text(torch.float16, 9, 64, 4) == "mx_down_sum f16 E9 P64 R9 A4"
+
+
+def _assert_walk_operands_exact(rows, x_dtype, w, bias, ids, unit):
+    """The conditions of tests/test_moe_host.py's exact cases on rows scaled by 2^-3: rows exact in their 16-bit type, weights that
+    quantise to their own codes, every block's partial sum and every output a multiple of the unit, the sum of the magnitudes below
+    2^24 units: exact in f32 in any order"""
+    E, N, K = w.shape
+    assert (cases.to_dtype(rows, x_dtype).double().numpy() == rows).all()
+    codes, scales = cases.quantize_experts(w)
+    assert (moe_cases.decode_experts(codes, scales) == w).all()
+    w2 = w.reshape(E * N, K)
+    total = np.abs(rows) @ np.abs(w2).T + (0 if bias is None else np.abs(bias).reshape(-1)[None, :])
+    assert total.max() / unit < 2.0 ** 24, total.max()
+    blocks = np.einsum("mbk,nbk->mnb", rows.reshape(rows.shape[0], -1, 32), w2.reshape(E * N, -1, 32))
+    assert (blocks % unit == 0).all() and (blocks.sum(axis=2) == rows @ w2.T).all()
+    pre = moe_cases.reference_f64(rows.reshape(ids.shape[0], -1, K) if rows.shape[0] == ids.size else rows, w, bias, ids)
+    assert (pre % unit == 0).all() and (pre.astype(F32) == pre).all()
+    return pre
+
+
+@pytest.mark.parametrize("index", range(len(cases.WALK_KS)))
+def test_every_walk_case_of_both_epilogues_is_exact_in_f32_in_any_order(index):
+    K = cases.WALK_KS[index]
+    assert 3104 * 144 * 0.125 / 2.0 ** -7 < 2.0 ** 24         # the worst case of lossless rows at the longest K
+    case = cases.WALK_GLU_CASES[index]
+    assert case[:6] == (3, cases.TILE // 2 + 1, K, 11, 3, (17, 0, 16))
+    x, w, bias, ids = cases.glu_operands(case, cases.WALK_SEED + index)
+    assert np.bincount(ids.reshape(-1), minlength=3).tolist() == [17, 0, 16] and w.shape == (3, 18, K)
+    pre = _assert_walk_operands_exact(x, case[6], w, bias, ids, 2.0 ** -7)
+    assert (pre < -cases.LIMIT).any() and (np.abs(pre) < cases.LIMIT).any() and (pre > cases.LIMIT).any()
+    case = cases.WALK_SUM_CASES[index]
+    assert case[:6] == (3, cases.TILE + 1, K, 11, 3, (17, 0, 16))
+    h, w, bias, ids, rw = cases.sum_operands(case, cases.WALK_SEED + index)
+    assert h.shape == (11, 3, K) and set(rw.reshape(-1).tolist()) >= set(cases.RW_SPECIALS)
+    for dtype in cases.DTYPES:
+        assert (cases.to_dtype(rw, dtype).double().numpy() == rw).all()
+    _assert_walk_operands_exact(h.reshape(-1, K), case[6], w, bias, ids, 2.0 ** -7)
+
+
+def test_the_walk_cases_alternate_every_form():
+    G, S = cases.WALK_GLU_CASES, cases.WALK_SUM_CASES
+    assert cases.WALK_KS is moe_cases.WALK_KS and [c[2] for c in G] == list(cases.WALK_KS) == [c[2] for c in S]
+    for table in (G, S):
+        assert {c[6] for c in table} == set(cases.X16) and {c[7] for c in table} == set(cases.DTYPES) and {c[8] for c in table} == {True, False}
+        assert all(table[i][6] != table[i + 1][6] and table[i][7] != table[i + 1][7] for i in range(len(table) - 1))
+    assert {c[9] for c in G} == {cases.LIMIT, INF} and {c[9] for c in S} == set(cases.DTYPES)
+    assert not set(cases.WALK_KS) & ({c[2] for c in cases.GLU_CASES} | {c[2] for c in cases.SUM_CASES})
