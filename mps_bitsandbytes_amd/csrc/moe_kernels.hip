@@ -119,7 +119,7 @@ int mbnb_moe_mxfp4_experts(const void *x, int64_t T, int64_t A, int x_per_slot, 
     const int st = x_dtype == MBNB_MOE_BF16 ? launch_experts<bf16_t>(x, w_codes, w_scales, ids, P, x_div, E, N, K, bias, bias_dtype, out, out_dtype, s)
                                             : launch_experts<f16_t>(x, w_codes, w_scales, ids, P, x_div, E, N, K, bias, bias_dtype, out, out_dtype, s);
     if (st == 0)
-        snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, "mx_experts %s %s E%lld P%lld", x_dtype == MBNB_MOE_BF16 ? "bf16" : "f16",
+        snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, "mx_experts %s %s E%lld P%lld", mbnb::mx::name16(x_dtype),
                  x_per_slot ? "slot" : "shared", (long long)E, (long long)P);
     return st;
 }

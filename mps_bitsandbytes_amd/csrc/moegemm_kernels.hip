@@ -11,14 +11,17 @@
 //                               MFMAs.  A result's bits are those of k_mx_experts for its row: the same blocks in the same
 //                               order on the same wave, one FMA by the scale per block, the eight partial sums added from
 //                               +0.0 in wave order.  Three epilogues: Plain (bias, one rounding, zeros for the out-of-range
-//                               pairs), Glu (moemlp_kernels.hip's gated activation) and PlainF32 (into the workspace).
-//   k_routed_sum                moemlp_kernels.hip's: the fmaf chain over the slots of a token, in slot order.
+//                               pairs), Glu (mx_experts.h's glu_store, the decode route's) and PlainF32 (into the workspace).
+//   k_routed_sum                mx_experts.h's, shared with moemlp_kernels.hip: the fmaf chain over the slots of a token, in
+//                               slot order.
 #include "../../include/mbnb_moegemm.h"
 #include "host.h"
 #include "mx_decode.h"
+#include "mx_experts.h"
 
 static_assert(MBNB_MOEGEMM_F16 == mbnb::kF16 && MBNB_MOEGEMM_BF16 == mbnb::kBF16 && MBNB_MOEGEMM_F32 == mbnb::kF32, "host.h's dtype codes");
 static_assert(MBNB_MOEGEMM_ERR_ARG == mbnb::mx::kErrArg && MBNB_MOEGEMM_ERR_SHAPE == mbnb::mx::kErrShape, "mx_decode.h's statuses");
+static_assert(MBNB_MOEGEMM_ERR_WORKSPACE == mbnb::mx::kErrWorkspace, "mx_experts.h's status");
 static_assert(MBNB_MOEGEMM_ROW_TILE % 16 == 0 && MBNB_MOEGEMM_ROW_TILE % 32 == 0, "whole A fragments, and 8 waves share the 4 R / 16 sums of a round");
 static_assert(MBNB_MOEGEMM_MAX_PAIRS >= 65536 && (int64_t)MBNB_MOEGEMM_MAX_PAIRS * 4 < INT32_MAX, "a pair index and a list offset are an int");
 
@@ -30,17 +33,25 @@ using mbnb::fail;
 using mbnb::mx::v4f;
 using mbnb::mx::v4i;
 using mbnb::mx::kMfmaWaves;
-using mbnb::mx::kNaNScale;
 using mbnb::mx::kOneScale;
 using mbnb::mx::decode8_16;
 using mbnb::mx::mfma16;
-using mbnb::mx::scale_value;
+using mbnb::mx::transpose_blocks;
+using mbnb::mx::block_scale;
+using mbnb::mx::BlockScale;
 using mbnb::mx::load_bias;
 using mbnb::mx::store_out;
 using mbnb::mx::lane_rank;
 using mbnb::mx::check_expert_call;
 using mbnb::mx::check_expert_nulls;
 using mbnb::mx::check_expert_alignment;
+using mbnb::mx::name16;
+using mbnb::mx::glu_store;
+using mbnb::mx::known_dtype;
+using mbnb::mx::ws_bytes;
+using mbnb::mx::check_glu_params;
+using mbnb::mx::check_workspace;
+using mbnb::mx::launch_routed_sum;
 
 constexpr int kMaxExperts = MBNB_MOEGEMM_MAX_EXPERTS;
 constexpr int kMaxGroupedPairs = MBNB_MOEGEMM_MAX_PAIRS;
@@ -51,7 +62,6 @@ constexpr int kColTile = 16 * kNT;
 constexpr int kThreads = 64 * kMfmaWaves;
 constexpr int kPlanThreads = 256, kPlanWaves = kPlanThreads / 64;
 constexpr int kPlanUnroll = 4;                           // id chunks of 256 whose loads are requested before the first ballot
-constexpr int kSumThreads = 256;
 
 struct Plain { static constexpr bool kGlu = false, kZeros = true; };
 struct Glu { static constexpr bool kGlu = true, kZeros = true; };
@@ -158,18 +168,6 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_fill(const int32_t *__res
 }
 
 // ---------------------------------------------------------------- the grouped GEMM
-// The gated activation, every operation a separate f32 rounding (-ffp-contract=off), the division IEEE, expf OCML's.
-__device__ __forceinline__ float glu(float g, float u, float alpha, float limit) {
-    g = g > limit ? limit : g;
-    u = u > limit ? limit : (u < -limit ? -limit : u);
-    const float t = alpha * g;
-    const float den = 1.0f + expf(-t);
-    const float sig = 1.0f / den;
-    const float gs = g * sig;
-    const float up = u + 1.0f;
-    return up * gs;
-}
-
 struct GroupedLds {                    // one round of the reduction: the 4 MT sums of one B fragment, of every wave
     float red[kMfmaWaves][4 * kMT][64];
     int red_ff[kMfmaWaves][64];
@@ -259,24 +257,18 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
         }
 #pragma unroll
         for (int j = 0; j < kNT; ++j) {
-            // register q of lane group g holds dword q of block g; after the transpose, dword g of block q
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            const v2u s02 = __builtin_amdgcn_permlane32_swap((unsigned)wq[j][0], (unsigned)wq[j][2], false, false);
-            const v2u s13 = __builtin_amdgcn_permlane32_swap((unsigned)wq[j][1], (unsigned)wq[j][3], false, false);
-            const v2u t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-            const v2u t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-            const uint32_t wb[4] = {t01[0], t01[1], t23[0], t23[1]};
+            uint32_t wb[4];
+            transpose_blocks(wq[j], wb);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const v4i bq = decode8_16<T>(wb[q]);
-                const uint32_t byte = (sb[j] >> (8 * q)) & 0xFFu;
-                ff[j] |= byte == (uint32_t)kNaNScale;
-                const float sv = scale_value(byte == (uint32_t)kNaNScale ? (uint32_t)kOneScale : byte);
+                const BlockScale bs = block_scale((sb[j] >> (8 * q)) & 0xFFu, ff[j]);
+                ff[j] = bs.ff;
 #pragma unroll
                 for (int m = 0; m < kMT; ++m) {
                     const v4f d = mfma16(xa[q][m], bq, T{});
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[m][j][r] = __builtin_fmaf(d[r], sv, acc[m][j][r]);
+                    for (int r = 0; r < 4; ++r) acc[m][j][r] = __builtin_fmaf(d[r], bs.sv, acc[m][j][r]);
                 }
                 __builtin_amdgcn_sched_barrier(0);           // the MT results of one block are consumed before the next block's are made
             }
@@ -309,10 +301,8 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
             const bool live = i < rows;
             const int64_t pair = sorted[first + (live ? i : 0)];
             const float pre = col_nan ? __uint_as_float(0x7FC00000u) : s + b;
-            if (EPI::kGlu) {
-                // N = 2I: lanes fr, fr ^ 1 hold (gate, up) of one output, both inside N or both outside; all 64 lanes exchange
-                const float other = __shfl_xor(pre, 1);
-                if (!(fr & 1) && col < N && live) store_out(out, out_dtype, pair * width + col / 2, glu(pre, other, alpha, limit));
+            if (EPI::kGlu) {                                 // every wave is here, whole: all 64 lanes exchange
+                glu_store(pre, fr, col < N && live, out, out_dtype, pair, N, col, alpha, limit);
             } else if (col < N && live) {
                 store_out(out, out_dtype, pair * width + n, pre);
             }
@@ -320,27 +310,7 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
     }
 }
 
-// One thread per out[t, n].  A skipped pair's routing weight and workspace row are not read.
-__global__ __launch_bounds__(kSumThreads) void k_routed_sum(const float *__restrict__ ws, const int32_t *__restrict__ ids,
-                                                            const void *__restrict__ rw, int rw_dtype, int64_t T, int A, int E, int64_t N,
-                                                            void *__restrict__ out, int out_dtype) {
-    const int64_t i = (int64_t)blockIdx.x * kSumThreads + threadIdx.x;
-    if (i >= T * N) return;
-    const int64_t t = i / N, n = i - t * N;
-    float acc = 0.0f;
-    for (int a = 0; a < A; ++a) {
-        const int64_t p = t * A + a;
-        const int id = ids[p];
-        if (id < 0 || id >= E) continue;
-        acc = __builtin_fmaf(load_bias(rw, rw_dtype, p), ws[p * N + n], acc);
-    }
-    store_out(out, out_dtype, i, acc);
-}
-
 // ---------------------------------------------------------------- host side
-bool known_dtype(int d) { return d >= MBNB_MOEGEMM_F16 && d <= MBNB_MOEGEMM_F32; }
-const char *name16(int d) { return d == MBNB_MOEGEMM_BF16 ? "bf16" : "f16"; }
-int64_t ws_bytes(int64_t P, int64_t N) { return mbnb::round256(P * N * 4); }
 int64_t plan_bytes_of(int64_t P, int64_t E) { return mbnb::round256(plan_words(P, E) * 4); }
 
 // The shape checks of a projection call: mx_decode.h's for everything but the pairs (asked with none, its limit being the decode
@@ -450,8 +420,7 @@ int mbnb_moegemm_gate_up_glu(const void *x, int64_t T, int64_t A, int64_t K, int
     if (I <= 0 || I > mbnb::kMaxElems / 2) return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: I = %lld", what, (long long)I);
     const int64_t N = 2 * I;
     if (const int st = check_grouped_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype)) return st;
-    if (!(alpha - alpha == 0.0f)) return fail(MBNB_MOEGEMM_ERR_ARG, "%s: alpha = %g is not finite", what, (double)alpha);
-    if (!(limit > 0.0f)) return fail(MBNB_MOEGEMM_ERR_ARG, "%s: limit = %g is not positive (+Inf: no clamp)", what, (double)limit);
+    if (const int st = check_glu_params(what, alpha, limit)) return st;
     const int64_t P = T * A;
     if (P == 0) return 0;
     const std::initializer_list<mbnb::mx::Operand> operands = {{"x", x, 16}, {"w_codes", w_codes, 16}, {"w_scales", w_scales, 1}, {"ids", ids, 4},
@@ -489,17 +458,13 @@ int mbnb_moegemm_down_sum(const void *h, int64_t T, int64_t A, int64_t K, int h_
                                                                {"bias", bias, mbnb::esize(bias_dtype), true}, {"workspace", workspace, 16, true},
                                                                {"plan", plan, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (!workspace || workspace_bytes < ws_bytes(P, N))
-        return fail(MBNB_MOEGEMM_ERR_WORKSPACE, "%s: the workspace is NULL or holds %lld bytes, %lld needed", what, (long long)workspace_bytes,
-                    (long long)ws_bytes(P, N));
+    if (const int st = check_workspace(what, workspace, workspace_bytes, P, N)) return st;
     if (const int st = check_plan(what, plan, plan_bytes, P, E)) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     hipStream_t s = (hipStream_t)stream;
     int st = launch_by_dtype<PlainF32>(h_dtype, h, w_codes, w_scales, plan, P, 1, E, N, K, bias, bias_dtype, workspace, MBNB_MOEGEMM_F32, 0.0f, 0.0f, s);
     if (st != 0) return st;
-    hipLaunchKernelGGL(k_routed_sum, dim3((unsigned)((T * N + kSumThreads - 1) / kSumThreads)), dim3(kSumThreads), 0, s, (const float *)workspace,
-                       ids, rw, rw_dtype, T, (int)A, (int)E, N, out, out_dtype);
-    st = mbnb::launch_status("k_routed_sum");
+    st = launch_routed_sum(workspace, ids, rw, rw_dtype, T, A, E, N, out, out_dtype, s);
     if (st == 0)
         snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, "mx_grouped_down_sum %s E%lld P%lld R%d A%lld", name16(h_dtype), (long long)E,
                  (long long)P, kRowTile, (long long)A);

@@ -6,16 +6,19 @@
 //                    (a presence byte per expert in LDS, walked 64 experts per step with a ballot), leaves when there are fewer,
 //                    and is k_mx_experts' workgroup from there on: the one pair list and the one decode tile of mx_decode.h, so
 //                    `pre` carries the bits that kernel writes in f32.  Two epilogues: Glu exchanges the (gate, up) columns of
-//                    a tile between neighbour lanes and stores the gated activation; PlainF32 stores the f32 value into the
-//                    workspace.
-//   k_routed_sum     out[t, n] = the fmaf chain over the slots of token t, in slot order, one thread per output.
+//                    a tile between neighbour lanes and stores the gated activation (mx_experts.h's glu_store); PlainF32
+//                    stores the f32 value into the workspace.
+//   k_routed_sum     mx_experts.h's, shared with moegemm_kernels.hip: out[t, n] = the fmaf chain over the slots of token t, in
+//                    slot order, one thread per output.
 #include "../../include/mbnb_moemlp.h"
 #include "host.h"
 #include "mx_decode.h"
+#include "mx_experts.h"
 
 static_assert(MBNB_MOEMLP_F16 == mbnb::kF16 && MBNB_MOEMLP_BF16 == mbnb::kBF16 && MBNB_MOEMLP_F32 == mbnb::kF32, "host.h's dtype codes");
 static_assert(MBNB_MOEMLP_MAX_PAIRS == mbnb::mx::kMaxPairs, "mx_decode.h's pair list");
 static_assert(MBNB_MOEMLP_ERR_ARG == mbnb::mx::kErrArg && MBNB_MOEMLP_ERR_SHAPE == mbnb::mx::kErrShape, "mx_decode.h's statuses");
+static_assert(MBNB_MOEMLP_ERR_WORKSPACE == mbnb::mx::kErrWorkspace, "mx_experts.h's status");
 static_assert(MBNB_MOEMLP_MAX_EXPERTS == 1024, "the presence array is zeroed by 256 threads, 4 bytes each");
 
 namespace {
@@ -40,24 +43,18 @@ using mbnb::mx::check_expert_call;
 using mbnb::mx::check_expert_pointers;
 using mbnb::mx::check_expert_nulls;
 using mbnb::mx::check_expert_alignment;
+using mbnb::mx::name16;
+using mbnb::mx::glu_store;
+using mbnb::mx::known_dtype;
+using mbnb::mx::ws_bytes;
+using mbnb::mx::check_glu_params;
+using mbnb::mx::check_workspace;
+using mbnb::mx::launch_routed_sum;
 
 constexpr int kMaxExperts = MBNB_MOEMLP_MAX_EXPERTS;
-constexpr int kSumThreads = 256;
 
 struct Glu { static constexpr bool kGlu = true; };
 struct PlainF32 { static constexpr bool kGlu = false; };
-
-// The gated activation, every operation a separate f32 rounding (-ffp-contract=off), the division IEEE, expf OCML's.
-__device__ __forceinline__ float glu(float g, float u, float alpha, float limit) {
-    g = g > limit ? limit : g;
-    u = u > limit ? limit : (u < -limit ? -limit : u);
-    const float t = alpha * g;
-    const float den = 1.0f + expf(-t);
-    const float sig = 1.0f / den;
-    const float gs = g * sig;
-    const float up = u + 1.0f;
-    return up * gs;
-}
 
 // Workgroup (tile, j).  The expert: every id in [0, E) sets its presence byte (plain stores of the same value: no order matters),
 // and after the barrier every wave walks the bytes 64 experts per step, so every wave knows `e` without another barrier.  From
@@ -134,11 +131,8 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void k_mx_experts_rt(const T *__re
             for (int r = 0; r < 4; ++r) {
                 const int i = c16 + 4 * g + r;
                 const float pre = col_nan ? __uint_as_float(0x7FC00000u) : s[r] + b;
-                if (EPI::kGlu) {
-                    // N = 2I: lanes fr, fr ^ 1 hold (gate, up) of one output, both inside N or both outside; all 64 lanes exchange
-                    const float other = __shfl_xor(pre, 1);
-                    if (!(fr & 1) && n0 + fr < N && i < count)
-                        store_out(out, out_dtype, (int64_t)list[i] * (N / 2) + (n0 + fr) / 2, glu(pre, other, alpha, limit));
+                if (EPI::kGlu) {                             // wave 0 alone is here, whole: all of its 64 lanes exchange
+                    glu_store(pre, fr, n0 + fr < N && i < count, out, out_dtype, (int64_t)list[i], N, n0 + fr, alpha, limit);
                 } else if (n0 + fr < N && i < count) {
                     ((float *)out)[(int64_t)list[i] * N + n] = pre;
                 }
@@ -148,27 +142,7 @@ __global__ __launch_bounds__(64 * kMfmaWaves) void k_mx_experts_rt(const T *__re
     }
 }
 
-// One thread per out[t, n].  A skipped pair's routing weight and workspace row are not read.
-__global__ __launch_bounds__(kSumThreads) void k_routed_sum(const float *__restrict__ ws, const int32_t *__restrict__ ids,
-                                                            const void *__restrict__ rw, int rw_dtype, int64_t T, int A, int E, int64_t N,
-                                                            void *__restrict__ out, int out_dtype) {
-    const int64_t i = (int64_t)blockIdx.x * kSumThreads + threadIdx.x;
-    if (i >= T * N) return;
-    const int64_t t = i / N, n = i - t * N;
-    float acc = 0.0f;
-    for (int a = 0; a < A; ++a) {
-        const int64_t p = t * A + a;
-        const int id = ids[p];
-        if (id < 0 || id >= E) continue;
-        acc = __builtin_fmaf(load_bias(rw, rw_dtype, p), ws[p * N + n], acc);
-    }
-    store_out(out, out_dtype, i, acc);
-}
-
 // ---------------------------------------------------------------- host side
-bool known_dtype(int d) { return d >= MBNB_MOEMLP_F16 && d <= MBNB_MOEMLP_F32; }
-const char *name16(int d) { return d == MBNB_MOEMLP_BF16 ? "bf16" : "f16"; }
-
 template <typename T, typename EPI>
 int launch_rt(const void *x, const void *W, const void *Ws, const int32_t *ids, int64_t P, int64_t x_div, int64_t E, int64_t N, int64_t K,
               const void *bias, int bias_dtype, void *out, int out_dtype, float alpha, float limit, hipStream_t s) {
@@ -177,8 +151,6 @@ int launch_rt(const void *x, const void *W, const void *Ws, const int32_t *ids, 
                        (const uint8_t *)Ws, ids, (int)P, (int)x_div, (int)E, N, K, bias, bias_dtype, out, out_dtype, (int)tiles, alpha, limit);
     return mbnb::launch_status("k_mx_experts_rt");
 }
-
-int64_t ws_bytes(int64_t P, int64_t N) { return mbnb::round256(P * N * 4); }
 
 }  // namespace
 
@@ -197,8 +169,7 @@ int mbnb_moemlp_gate_up_glu(const void *x, int64_t T, int64_t A, int64_t K, int 
     if (I <= 0 || I > mbnb::kMaxElems / 2) return fail(MBNB_MOEMLP_ERR_SHAPE, "%s: I = %lld", what, (long long)I);
     const int64_t N = 2 * I;
     if (const int st = check_expert_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype, kMaxExperts, true)) return st;
-    if (!(alpha - alpha == 0.0f)) return fail(MBNB_MOEMLP_ERR_ARG, "%s: alpha = %g is not finite", what, (double)alpha);
-    if (!(limit > 0.0f)) return fail(MBNB_MOEMLP_ERR_ARG, "%s: limit = %g is not positive (+Inf: no clamp)", what, (double)limit);
+    if (const int st = check_glu_params(what, alpha, limit)) return st;
     const int64_t P = T * A;
     if (P == 0) return 0;
     if (const int st = check_expert_pointers(what, {{"x", x, 16}, {"w_codes", w_codes, 16}, {"w_scales", w_scales, 1}, {"ids", ids, 4},
@@ -236,18 +207,14 @@ int mbnb_moemlp_down_sum(const void *h, int64_t T, int64_t A, int64_t K, int h_d
                                                                {"rw", rw, mbnb::esize(rw_dtype)}, {"out", out, mbnb::esize(out_dtype)},
                                                                {"bias", bias, mbnb::esize(bias_dtype), true}, {"workspace", workspace, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (!workspace || workspace_bytes < ws_bytes(P, N))
-        return fail(MBNB_MOEMLP_ERR_WORKSPACE, "%s: the workspace is NULL or holds %lld bytes, %lld needed", what, (long long)workspace_bytes,
-                    (long long)ws_bytes(P, N));
+    if (const int st = check_workspace(what, workspace, workspace_bytes, P, N)) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     hipStream_t s = (hipStream_t)stream;
     int st = h_dtype == MBNB_MOEMLP_BF16
                  ? launch_rt<bf16_t, PlainF32>(h, w_codes, w_scales, ids, P, 1, E, N, K, bias, bias_dtype, workspace, MBNB_MOEMLP_F32, 0.0f, 0.0f, s)
                  : launch_rt<f16_t, PlainF32>(h, w_codes, w_scales, ids, P, 1, E, N, K, bias, bias_dtype, workspace, MBNB_MOEMLP_F32, 0.0f, 0.0f, s);
     if (st != 0) return st;
-    hipLaunchKernelGGL(k_routed_sum, dim3((unsigned)((T * N + kSumThreads - 1) / kSumThreads)), dim3(kSumThreads), 0, s, (const float *)workspace,
-                       ids, rw, rw_dtype, T, (int)A, (int)E, N, out, out_dtype);
-    st = mbnb::launch_status("k_routed_sum");
+    st = launch_routed_sum(workspace, ids, rw, rw_dtype, T, A, E, N, out, out_dtype, s);
     if (st == 0)
         snprintf(mbnb::last_launch(), mbnb::kLaunchBytes, "mx_down_sum %s E%lld P%lld R%lld A%lld", name16(h_dtype), (long long)E, (long long)P,
                  (long long)(E < P ? E : P), (long long)A);

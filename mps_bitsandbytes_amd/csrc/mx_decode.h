@@ -1,11 +1,14 @@
-// mx_decode.h — what the three MXFP4 decode libraries share: mx_kernels.hip (k_mx_decode, k_mx_decode_mfma),
-// moe_kernels.hip (k_mx_experts) and moemlp_kernels.hip (k_mx_experts_rt).
+// mx_decode.h — what the four MXFP4 decode libraries share: mx_kernels.hip (k_mx_decode,
+// k_mx_decode_mfma), moe_kernels.hip (k_mx_experts), moemlp_kernels.hip (k_mx_experts_rt) and moegemm_kernels.hip
+// (k_mx_experts_grouped); the last two through mx_experts.h, which adds what only the expert MLP shares.
 //
 //   device   the E8M0 scale, the byte-table decode of 8 E2M1 codes to 8 values of the activation's 16-bit type, the MFMA of one MX
-//            block, the bias load and output store by dtype code; and the ONE text of the 16 x 16 decode tile on
-//            v_mfma_f32_16x16x32: tile_walk (a wave's share of the K walk) and tile_reduce (the eight partial sums, in wave order),
-//            which fix a result's bits, and list_pairs (the id scan of the two expert kernels).  All of it forced inline.
-//   host     check_expert_call / check_expert_pointers: the argument checks the three expert entry points share.
+//            block, the bias load and output store by dtype code; transpose_blocks (the 4 x 4 transpose of a k-step's weight
+//            bytes across the lane groups) and block_scale (the scale rule of one block, 0xFF included); and the ONE text of the
+//            16 x 16 decode tile on v_mfma_f32_16x16x32: tile_walk (a wave's share of the K walk) and tile_reduce (the eight
+//            partial sums, in wave order), which fix a result's bits, and list_pairs (the id scan of the two decode-route expert
+//            kernels).  All of it forced inline.
+//   host     check_expert_call / check_expert_pointers: the argument checks the expert entry points share; name16.
 // The dtype codes are host.h's, which every public header restates.
 #pragma once
 
@@ -64,6 +67,28 @@ __device__ __forceinline__ v4f mfma16(v4i a, v4i b, f16_t) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
 }
 
+// The 4 x 4 transpose across the four lane groups: register q of lane group g holds dword q of block g (the 16 bytes the lane
+// fetched); after it wb[q] holds dword g of block q, the B fragment of the MFMA of block q.
+__device__ __forceinline__ void transpose_blocks(v4i wq, uint32_t (&wb)[4]) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const v2u s02 = __builtin_amdgcn_permlane32_swap((unsigned)wq[0], (unsigned)wq[2], false, false);
+    const v2u s13 = __builtin_amdgcn_permlane32_swap((unsigned)wq[1], (unsigned)wq[3], false, false);
+    const v2u t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
+    const v2u t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
+    wb[0] = t01[0], wb[1] = t01[1], wb[2] = t23[0], wb[3] = t23[1];
+}
+
+// The scale rule of one block: a 0xFF byte sets `ff` (the column is NaN) and the block counts with the scale 2^0.  The running
+// `ff` goes in and comes out by value: through a reference the compiler allocates tile_walk's registers otherwise.
+struct BlockScale {
+    float sv;
+    bool ff;
+};
+__device__ __forceinline__ BlockScale block_scale(uint32_t byte, bool ff) {
+    ff |= byte == (uint32_t)kNaNScale;
+    return BlockScale{scale_value(byte == (uint32_t)kNaNScale ? (uint32_t)kOneScale : byte), ff};
+}
+
 // ---------------------------------------------------------------- the 16 x 16 decode tile of an 8-wave workgroup
 // A workgroup owns 16 weight rows and ALL of K against up to 16 activation rows.  Lane (fr = l & 15, g = l >> 4) of every wave
 // holds weight row fr (w_row, s_row: its codes and scale bytes) and activation row fr (x_row, already advanced by 8 g elements;
@@ -112,21 +137,15 @@ __device__ __forceinline__ TileSums tile_walk(const T *x_row, bool x_live, const
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (c0 + u * kMfmaWaves >= steps) break;         // wave-uniform
-            // register q of lane group g holds dword q of block g; after the transpose, dword g of block q
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
-            const v2u s02 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][0], (unsigned)wq[u][2], false, false);
-            const v2u s13 = __builtin_amdgcn_permlane32_swap((unsigned)wq[u][1], (unsigned)wq[u][3], false, false);
-            const v2u t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-            const v2u t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-            const uint32_t wb[4] = {t01[0], t01[1], t23[0], t23[1]};
+            uint32_t wb[4];
+            transpose_blocks(wq[u], wb);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const v4f d = mfma16(xa[u][q], decode8_16<T>(wb[q]), T{});
-                const uint32_t byte = sb[u][q];
-                ff |= byte == (uint32_t)kNaNScale;
-                const float sv = scale_value(byte == (uint32_t)kNaNScale ? (uint32_t)kOneScale : byte);
+                const BlockScale bs = block_scale(sb[u][q], ff);
+                ff = bs.ff;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(d[r], sv, acc[r]);
+                for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(d[r], bs.sv, acc[r]);
             }
         }
     }
@@ -193,6 +212,8 @@ __device__ __forceinline__ PairCounts list_pairs(const int32_t *ids, int P, int 
 // ---------------------------------------------------------------- host: the checks of an expert call
 // The statuses of mbnb_moe.h and mbnb_moemlp.h, which agree: each library asserts its own against these.
 constexpr int kErrArg = -1, kErrShape = -2;
+
+static inline const char *name16(int dtype) { return dtype == kBF16 ? "bf16" : "f16"; }   // of 16-bit rows, in a last_launch() text
 
 // Rows [., K] of `row_dtype` against [E, N, K] weights for T x A pairs: 0, or the status recorded under the entry point's name.
 // max_experts: the library's limit on E, 0 for none.  routed_grid: the launch has ceil(N / 16) x min(E, P) workgroups, else

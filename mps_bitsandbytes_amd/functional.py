@@ -1982,6 +1982,16 @@ def matmul_mxfp4(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Opt
 # picks `top_k` of the E experts per token.  One launch of libmbnb_moe.so serves a projection of every (token, slot) pair, the
 # expert ids read on the device.  _expert_operands is the one check and preparation of an expert projection's
 # operands, for this call and for the two of the MLP below.
+def _check_expert_ids(what: str, expert_ids: Tensor) -> None:
+    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
+        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
+
+
+def _int32_ids(ids: Tensor) -> Tensor:
+    """The ids as the int32 contiguous tensor the launches read: the caller's own when it is one already."""
+    return ids if ids.dtype == torch.int32 and ids.is_contiguous() else ids.to(torch.int32).contiguous()
+
+
 def _expert_operands(what: str, native, input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor],
                      per_slot: Optional[bool], dtype: Optional[torch.dtype], routing_weights: Optional[Tensor] = None):
     """The checks and the operand preparation of one expert projection -> (x, w, s, ids, b, rw, T, A, E, N, K, out dtype, its code).
@@ -2007,8 +2017,7 @@ def _expert_operands(what: str, native, input: Tensor, weight: Tensor, weight_sc
     if tuple(weight_scales.shape) != (E, N, K // native.BLOCK):
         raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: "
                          f"expected {(E, N, K // native.BLOCK)}")
-    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
-        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
+    _check_expert_ids(what, expert_ids)
     T, A = expert_ids.shape
     if per_slot is None:
         if input.dim() not in (2, 3):
@@ -2034,9 +2043,7 @@ def _expert_operands(what: str, native, input: Tensor, weight: Tensor, weight_sc
     x = _aligned16(input)
     w = _aligned16(weight)
     s = weight_scales.to(x.device).contiguous()
-    ids = expert_ids.to(x.device)
-    if ids.dtype != torch.int32 or not ids.is_contiguous():
-        ids = ids.to(torch.int32).contiguous()
+    ids = _int32_ids(expert_ids.to(x.device))
     b = None if bias is None else bias.to(x.device).contiguous()
     if b is not None and b.dtype not in _native.DTYPE_CODE:
         b = b.float()
@@ -2064,23 +2071,8 @@ def matmul_mxfp4_experts(input: Tensor, weight: Tensor, weight_scales: Tensor, e
     grouped GEMM of `matmul_mxfp4_experts_grouped`: the same bits, another `last_launch()`.
     """
     what = "matmul_mxfp4_experts"
-    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moe_native, input, weight, weight_scales, expert_ids, bias, None,
-                                                                          dtype)
-    per_slot = x.dim() == 3
-    if _takes_grouped(T * A, E):
-        return _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, None)
-    out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
-    if T * A == 0:
-        return out
-    step = max(1, _moe_native.MAX_PAIRS // A)                # tokens per launch
-    fn = _moe_native.lib().mbnb_moe_mxfp4_experts
-    with on_device(x.device):
-        stream = stream_ptr(x.device)
-        for t0 in range(0, T, step):
-            t1 = min(T, t0 + step)
-            _moe_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
-                                 ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode, stream), what)
-    return out
+    ops = _expert_operands(what, _moe_native, input, weight, weight_scales, expert_ids, bias, None, dtype)
+    return _experts_plain(what, _ops_take_grouped(ops), ops)
 
 
 # ============================================================================= the MXFP4 mixture-of-experts MLP
@@ -2105,27 +2097,9 @@ def matmul_mxfp4_experts_glu(input: Tensor, weight: Tensor, weight_scales: Tenso
     takes the grouped GEMM of `matmul_mxfp4_experts_grouped_glu`: the same bits, another `last_launch()`.
     """
     what = "matmul_mxfp4_experts_glu"
-    alpha, limit = float(alpha), float(limit)
-    if not math.isfinite(alpha) or not limit > 0:
-        raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
-    if weight.dim() in (3, 4) and weight.shape[1] % 2:
-        raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
-    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, False, dtype)
-    I = N // 2
-    if _takes_grouped(T * A, E):
-        return _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, None)
-    out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
-    if T * A == 0:
-        return out
-    step = max(1, _moemlp_native.MAX_PAIRS // A)             # tokens per launch
-    fn = _moemlp_native.lib().mbnb_moemlp_gate_up_glu
-    with on_device(x.device):
-        stream = stream_ptr(x.device)
-        for t0 in range(0, T, step):
-            t1 = min(T, t0 + step)
-            _moemlp_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, I, ptr(ids[t0:t1]), ptr(b),
-                                    0 if b is None else _native.DTYPE_CODE[b.dtype], alpha, limit, ptr(out[t0:t1]), ocode, stream), what)
-    return out
+    alpha, limit = _glu_params(what, alpha, limit, weight)
+    ops = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, False, dtype)
+    return _experts_glu(what, _ops_take_grouped(ops), ops, alpha, limit)
 
 
 def matmul_mxfp4_experts_sum(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
@@ -2145,25 +2119,8 @@ def matmul_mxfp4_experts_sum(input: Tensor, weight: Tensor, weight_scales: Tenso
     `MOE_GROUPED_MIN_PAIRS` pairs up the call takes the grouped GEMM of `matmul_mxfp4_experts_grouped_sum`: the same bits.
     """
     what = "matmul_mxfp4_experts_sum"
-    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, True, dtype,
-                                                                           routing_weights)
-    if T * A == 0:
-        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
-    if _takes_grouped(T * A, E):
-        return _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, None)
-    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
-    step = max(1, _moemlp_native.MAX_PAIRS // A)             # tokens per call
-    ws_bytes = _moemlp_native.workspace_bytes(min(T, step), A, N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    fn = _moemlp_native.lib().mbnb_moemlp_down_sum
-    with on_device(x.device):
-        stream = stream_ptr(x.device)
-        for t0 in range(0, T, step):
-            t1 = min(T, t0 + step)
-            _moemlp_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b),
-                                    0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(rw[t0:t1]), _native.DTYPE_CODE[rw.dtype],
-                                    ptr(out[t0:t1]), ocode, ptr(ws), ws_bytes, stream), what)
-    return out
+    ops = _expert_operands(what, _moemlp_native, input, weight, weight_scales, expert_ids, bias, True, dtype, routing_weights)
+    return _experts_sum(what, _ops_take_grouped(ops), ops)
 
 
 def moe_mlp_mxfp4(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor, gate_up_bias: Optional[Tensor], down_weight: Tensor,
@@ -2177,15 +2134,16 @@ def moe_mlp_mxfp4(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor,
     From `MOE_GROUPED_MIN_PAIRS` pairs up both projections run on the grouped GEMM and
     share one plan of the routing per cut of `MOE_GROUPED_MAX_PAIRS` pairs: the same bits.
     """
-    if (expert_ids.dim() == 2 and expert_ids.is_cuda and not expert_ids.dtype.is_floating_point and gate_up_weight.dim() in (3, 4)
-            and down_weight.dim() in (3, 4) and gate_up_weight.shape[0] == down_weight.shape[0]
-            and _takes_grouped(expert_ids.numel(), gate_up_weight.shape[0])):
-        # the prefill route: one plan per cut over the tokens serves both projections
-        ids, plan = moe_grouped_plan(expert_ids, gate_up_weight.shape[0])
-        h = matmul_mxfp4_experts_grouped_glu(input, gate_up_weight, gate_up_scales, ids, gate_up_bias, alpha, limit, plan=plan)
-        return matmul_mxfp4_experts_grouped_sum(h, down_weight, down_scales, ids, routing_weights, down_bias, dtype, plan=plan)
-    h = matmul_mxfp4_experts_glu(input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, alpha, limit)
-    return matmul_mxfp4_experts_sum(h, down_weight, down_scales, expert_ids, routing_weights, down_bias, dtype)
+    up_what, down_what = "matmul_mxfp4_experts_glu", "matmul_mxfp4_experts_sum"
+    alpha, limit = _glu_params(up_what, alpha, limit, gate_up_weight)
+    up = _expert_operands(up_what, _moemlp_native, input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, False, None)
+    ids, T, A, E = up[3], up[6], up[7], up[8]
+    grouped = _ops_take_grouped(up)
+    # the prefill route: one plan per cut over the tokens serves both projections
+    plan = _grouped_plans("moe_grouped_plan", ids, T, A, E) if grouped and T * A else None
+    h = _experts_glu(up_what, grouped, up, alpha, limit, plan)
+    down = _expert_operands(down_what, _moemlp_native, h, down_weight, down_scales, ids, down_bias, True, dtype, routing_weights)
+    return _experts_sum(down_what, _ops_take_grouped(down), down, plan if down[8] == E else None)
 
 
 # ============================================================================= the prefill-sized grouped GEMM over MXFP4 experts
@@ -2205,9 +2163,18 @@ def _takes_grouped(pairs: int, E: int) -> bool:
     return MOE_GROUPED_MIN_PAIRS is not None and pairs >= max(1, MOE_GROUPED_MIN_PAIRS) and E <= _moegemm_native.MAX_EXPERTS
 
 
-def _grouped_cuts(T: int, A: int):
-    step = max(1, MOE_GROUPED_MAX_PAIRS // max(1, A))        # tokens per call
+def _ops_take_grouped(ops) -> bool:
+    """_takes_grouped for the pairs and experts of what _expert_operands returned."""
+    return _takes_grouped(ops[6] * ops[7], ops[8])
+
+
+def _cuts(T: int, A: int, max_pairs: int):
+    step = max(1, max_pairs // max(1, A))                    # tokens per call
     return [(t0, min(T, t0 + step)) for t0 in range(0, T, step)]
+
+
+def _grouped_cuts(T: int, A: int):
+    return _cuts(T, A, MOE_GROUPED_MAX_PAIRS)
 
 
 def moe_grouped_plan(expert_ids: Tensor, num_experts: int):
@@ -2219,8 +2186,7 @@ def moe_grouped_plan(expert_ids: Tensor, num_experts: int):
     after `expert_ids` changes in place, build it again.
     """
     what = "moe_grouped_plan"
-    if expert_ids.dim() != 2 or expert_ids.dtype.is_floating_point or expert_ids.dtype.is_complex or expert_ids.dtype == torch.bool:
-        raise ValueError(f"{what}: expert_ids must be an integer tensor [T, A], got {expert_ids.dtype} {tuple(expert_ids.shape)}")
+    _check_expert_ids(what, expert_ids)
     E = int(num_experts)
     if not 0 < E <= _moegemm_native.MAX_EXPERTS:
         raise ValueError(f"{what}: {E} experts, between 1 and {_moegemm_native.MAX_EXPERTS}")
@@ -2228,9 +2194,7 @@ def moe_grouped_plan(expert_ids: Tensor, num_experts: int):
     T, A = expert_ids.shape
     if A > _moegemm_native.MAX_PAIRS:
         raise ValueError(f"{what}: {A} slots per token exceed the {_moegemm_native.MAX_PAIRS} pairs of one launch")
-    ids = expert_ids
-    if ids.dtype != torch.int32 or not ids.is_contiguous():
-        ids = ids.to(torch.int32).contiguous()
+    ids = _int32_ids(expert_ids)
     return ids, _grouped_plans(what, ids, T, A, E)
 
 
@@ -2261,53 +2225,86 @@ def _grouped_plans_of(what: str, plan, ids: Tensor, T: int, A: int, E: int):
     return list(plan)
 
 
-def _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, plan):
-    per_slot = x.dim() == 3
+# The call loops of the three forms, for the decode route (§28 / §29) and the grouped one alike: a function allocates the output,
+# handles the empty call, cuts over the tokens and makes the native calls.  A route gives it data only (_expert_route): the
+# binding, the entry point, the cuts by its pairs per call, and the plan that trails the arguments of a grouped call.
+_EXPERT_ENTRY = {   # form -> (the decode binding, its entry point, the grouped entry point)
+    "plain": (_moe_native, "mbnb_moe_mxfp4_experts", "mbnb_moegemm_experts"),
+    "glu": (_moemlp_native, "mbnb_moemlp_gate_up_glu", "mbnb_moegemm_gate_up_glu"),
+    "sum": (_moemlp_native, "mbnb_moemlp_down_sum", "mbnb_moegemm_down_sum"),
+}
+
+
+def _expert_route(what: str, form: str, grouped: bool, plan, ids: Tensor, T: int, A: int, E: int):
+    """-> (binding, entry point, cuts over the tokens, the plan of each cut or None).  Not for an empty call."""
+    native, entry, grouped_entry = _EXPERT_ENTRY[form]
+    if grouped:
+        return _moegemm_native, getattr(_moegemm_native.lib(), grouped_entry), _grouped_cuts(T, A), _grouped_plans_of(what, plan, ids, T, A, E)
+    cuts = _cuts(T, A, native.MAX_PAIRS)
+    return native, getattr(native.lib(), entry), cuts, [None] * len(cuts)
+
+
+def _plan_args(q: Optional[Tensor]):
+    """What a grouped entry point takes after the decode one's arguments: the plan and its bytes."""
+    return () if q is None else (ptr(q), q.numel())
+
+
+def _glu_params(what: str, alpha: float, limit: float, weight: Tensor):
+    """The checks a gate / up projection adds to _expert_operands' -> (alpha, limit) as floats."""
+    alpha, limit = float(alpha), float(limit)
+    if not math.isfinite(alpha) or not limit > 0:
+        raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
+    if weight.dim() in (3, 4) and weight.shape[1] % 2:
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
+    return alpha, limit
+
+
+def _experts_plain(what: str, grouped: bool, ops, plan=None) -> Tensor:
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = ops
     out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
     if T * A == 0:
         return out
-    plans = _grouped_plans_of(what, plan, ids, T, A, E)
-    fn = _moegemm_native.lib().mbnb_moegemm_experts
+    native, fn, cuts, plans = _expert_route(what, "plain", grouped, plan, ids, T, A, E)
+    xcode, bcode, per_slot = dtype_code(x.dtype, what), 0 if b is None else _native.DTYPE_CODE[b.dtype], int(x.dim() == 3)
     with on_device(x.device):
         stream = stream_ptr(x.device)
-        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
-            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, int(per_slot), K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N,
-                                     ptr(ids[t0:t1]), ptr(b), 0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(out[t0:t1]), ocode,
-                                     ptr(q), q.numel(), stream), what)
+        for (t0, t1), q in zip(cuts, plans):
+            native.check(fn(ptr(x[t0:t1]), t1 - t0, A, per_slot, K, xcode, ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b), bcode,
+                            ptr(out[t0:t1]), ocode, *_plan_args(q), stream), what)
     return out
 
 
-def _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, plan):
+def _experts_glu(what: str, grouped: bool, ops, alpha: float, limit: float, plan=None) -> Tensor:
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = ops
     I = N // 2
     out = torch.empty(T, A, I, dtype=out_dtype, device=x.device)
     if T * A == 0:
         return out
-    plans = _grouped_plans_of(what, plan, ids, T, A, E)
-    fn = _moegemm_native.lib().mbnb_moegemm_gate_up_glu
-    with on_device(x.device):
-        stream = stream_ptr(x.device)
-        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
-            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, I, ptr(ids[t0:t1]), ptr(b),
-                                     0 if b is None else _native.DTYPE_CODE[b.dtype], alpha, limit, ptr(out[t0:t1]), ocode, ptr(q), q.numel(),
-                                     stream), what)
-    return out
-
-
-def _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, plan):
-    if T * A == 0:
-        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
-    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
-    plans = _grouped_plans_of(what, plan, ids, T, A, E)
-    cuts = _grouped_cuts(T, A)
-    ws_bytes = _moegemm_native.workspace_bytes((cuts[0][1] - cuts[0][0]) * A, N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    fn = _moegemm_native.lib().mbnb_moegemm_down_sum
+    native, fn, cuts, plans = _expert_route(what, "glu", grouped, plan, ids, T, A, E)
+    xcode, bcode = dtype_code(x.dtype, what), 0 if b is None else _native.DTYPE_CODE[b.dtype]
     with on_device(x.device):
         stream = stream_ptr(x.device)
         for (t0, t1), q in zip(cuts, plans):
-            _moegemm_native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, dtype_code(x.dtype, what), ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b),
-                                     0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(rw[t0:t1]), _native.DTYPE_CODE[rw.dtype],
-                                     ptr(out[t0:t1]), ocode, ptr(ws), ws_bytes, ptr(q), q.numel(), stream), what)
+            native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, xcode, ptr(w), ptr(s), E, I, ptr(ids[t0:t1]), ptr(b), bcode, alpha, limit,
+                            ptr(out[t0:t1]), ocode, *_plan_args(q), stream), what)
+    return out
+
+
+def _experts_sum(what: str, grouped: bool, ops, plan=None) -> Tensor:
+    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = ops
+    if T * A == 0:
+        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
+    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
+    native, fn, cuts, plans = _expert_route(what, "sum", grouped, plan, ids, T, A, E)
+    first = cuts[0][1] - cuts[0][0]                          # the first cut is the largest: its workspace serves them all
+    ws_bytes = native.workspace_bytes(first * A, N) if grouped else native.workspace_bytes(first, A, N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    xcode, bcode, rcode = dtype_code(x.dtype, what), 0 if b is None else _native.DTYPE_CODE[b.dtype], _native.DTYPE_CODE[rw.dtype]
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(cuts, plans):
+            native.check(fn(ptr(x[t0:t1]), t1 - t0, A, K, xcode, ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b), bcode, ptr(rw[t0:t1]), rcode,
+                            ptr(out[t0:t1]), ocode, ptr(ws), ws_bytes, *_plan_args(q), stream), what)
     return out
 
 
@@ -2323,9 +2320,8 @@ def matmul_mxfp4_experts_grouped(input: Tensor, weight: Tensor, weight_scales: T
     most 1024 experts.  Inference only.
     """
     what = "matmul_mxfp4_experts_grouped"
-    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
-                                                                          None, dtype)
-    return _grouped_experts(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, plan)
+    ops = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, None, dtype)
+    return _experts_plain(what, True, ops, plan)
 
 
 def matmul_mxfp4_experts_grouped_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
@@ -2335,14 +2331,9 @@ def matmul_mxfp4_experts_grouped_glu(input: Tensor, weight: Tensor, weight_scale
     ``[T, A, I]``; the gated activation is the epilogue of the one launch per cut.  `plan` as in `matmul_mxfp4_experts_grouped`.
     """
     what = "matmul_mxfp4_experts_grouped_glu"
-    alpha, limit = float(alpha), float(limit)
-    if not math.isfinite(alpha) or not limit > 0:
-        raise ValueError(f"{what}: alpha ({alpha}) must be finite and limit ({limit}) positive (inf: no clamp)")
-    if weight.dim() in (3, 4) and weight.shape[1] % 2:
-        raise ValueError(f"{what}: weight {tuple(weight.shape)} has {weight.shape[1]} rows: the interleaved gate / up rows come in pairs")
-    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
-                                                                          False, dtype)
-    return _grouped_glu(what, x, w, s, ids, b, T, A, E, N, K, out_dtype, ocode, alpha, limit, plan)
+    alpha, limit = _glu_params(what, alpha, limit, weight)
+    ops = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, False, dtype)
+    return _experts_glu(what, True, ops, alpha, limit, plan)
 
 
 def matmul_mxfp4_experts_grouped_sum(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
@@ -2353,9 +2344,8 @@ def matmul_mxfp4_experts_grouped_sum(input: Tensor, weight: Tensor, weight_scale
     rows), the routed sum over the slots follows as a second launch.  `plan` as in `matmul_mxfp4_experts_grouped`.
     """
     what = "matmul_mxfp4_experts_grouped_sum"
-    x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias,
-                                                                           True, dtype, routing_weights)
-    return _grouped_sum(what, x, w, s, ids, b, rw, T, A, E, N, K, out_dtype, ocode, plan)
+    ops = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, True, dtype, routing_weights)
+    return _experts_sum(what, True, ops, plan)
 
 
 # ============================================================================= the router of the mixture-of-experts block

@@ -669,6 +669,32 @@ def test_the_automatic_route_at_the_threshold_has_the_bits_of_the_decode_route(m
         _assert_bits(bnb.matmul_mxfp4_experts_sum(h, args[3], args[4], ids, rw, args[5]).cpu(), want_mlp, "the two halves")
 
 
+@pytest.mark.parametrize("dtype", cases.X16, ids=_name)
+@pytest.mark.parametrize("form", ("plain", "glu", "sum"))
+def test_one_call_loop_serves_both_routes_with_the_same_bits(form, dtype, monkeypatch):
+    """The automatic function with MOE_GROUPED_MIN_PAIRS = 1 (grouped) and None (decode) on the same operands: T = 9, A = 4, E = 5 with
+    an id of -1 and an id of E, K = 160 (the ragged step on wave 1), N = 50 (past one 48-column tile; I = 25 for the GLU form)"""
+    T, A, E, N, K = 9, 4, 5, 50, 160
+    x, h, w, s, bias, ids, rw = _surface(T, A, E, N, K, dtype, seed=43300)
+    ids = ids.clamp(min=0)
+    ids[2, 1], ids[7, 3] = -1, E
+    call = {"plain": lambda: bnb.matmul_mxfp4_experts(x, w, s, ids, bias), "glu": lambda: bnb.matmul_mxfp4_experts_glu(x, w, s, ids, bias),
+            "sum": lambda: bnb.matmul_mxfp4_experts_sum(h, w, s, ids, rw, bias)}[form]
+    with torch.no_grad():
+        monkeypatch.setattr(F, "MOE_GROUPED_MIN_PAIRS", None)
+        before = gn.last_launch()
+        decode = call()
+        assert gn.last_launch() == before
+        monkeypatch.setattr(F, "MOE_GROUPED_MIN_PAIRS", 1)
+        grouped = call()
+    text = {"plain": cases.experts_text(dtype, False, E, T * A), "glu": cases.glu_text(dtype, E, T * A), "sum": cases.down_text(dtype, E, T * A, A)}[form]
+    assert gn.last_launch() == text
+    assert tuple(decode.shape) == {"plain": (T, A, N), "glu": (T, A, N // 2), "sum": (T, N)}[form] and decode.dtype == dtype
+    assert torch.equal(decode.view(torch.int16), grouped.view(torch.int16)) and not torch.isnan(decode.float()).any()
+    if form != "sum":
+        assert _is_plus_zero(grouped[2, 1]) and _is_plus_zero(grouped[7, 3]) and not _is_plus_zero(grouped[2, 0])
+
+
 def test_a_captured_graph_of_the_block_on_the_grouped_route(monkeypatch):
     T, A, E, H, I = cases.ROUTE_SHAPE
     block, xs, rws = _route_block()

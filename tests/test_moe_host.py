@@ -83,7 +83,8 @@ def test_the_makefile_the_build_and_the_sources():
     # the decode tile, the pair list and the checks of an expert call are ONE text: defined in the header, called by the kernel files
     mlp_src = open(os.path.join(CSRC, "moemlp_kernels.hip")).read()
     kernels = {"mx_kernels.hip": mx_src, "moe_kernels.hip": src, "moemlp_kernels.hip": mlp_src}
-    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers"):
+    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers", "transpose_blocks",
+                 "block_scale"):
         definition = re.compile(r"^(?:__device__ __forceinline__|static) [\w ]+ " + name + r"\(", flags=re.M)
         assert len(definition.findall(shared)) == 1, name
         assert not any(definition.search(text) for text in kernels.values()), name

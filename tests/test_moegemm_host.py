@@ -1,7 +1,7 @@
 """CPU-side checks of the grouped GEMM over MXFP4 experts (libmbnb_moegemm.so, functional.matmul_mxfp4_experts_grouped / _glu / _sum;
 DESIGN.md §32), without a GPU: the C ABI (the header, the binding and the library agree; the library exports exactly its header and
 needs no other libmbnb_*; every argument error is a status before any device access), the numpy plan of tests/moegemm_cases.py and
-the tile bound, the restated glu and routed-sum bodies, the Python surface and the case tables."""
+the tile bound, the one definition of the glu and routed-sum bodies, the Python surface and the case tables."""
 import inspect
 import itertools
 import os
@@ -84,14 +84,20 @@ def test_the_makefile_the_build_and_the_source():
         assert "set_kernel_name" not in text and "set_kernel_variant" not in text, path
         assert "atomic" not in text.lower() and "asm" not in text, path
     includes = re.findall(r'#include\s+[<"]([^>"]+)[>"]', src)
-    assert includes == ["../../include/mbnb_moegemm.h", "host.h", "mx_decode.h"]
+    assert includes == ["../../include/mbnb_moegemm.h", "host.h", "mx_decode.h", "mx_experts.h"]
     assert "mbnb_moegemm_last_launch" in src and "last_launch()" in src
     for kernel in ("k_plan_count", "k_plan_fill", "k_mx_experts_grouped", "k_routed_sum"):
         assert kernel in src, kernel
     shared = open(os.path.join(CSRC, "mx_decode.h")).read()
-    for name in ("decode8_16", "mfma16", "scale_value", "load_bias", "store_out", "lane_rank", "check_expert_call"):    # called, not restated
+    for name in ("decode8_16", "mfma16", "transpose_blocks", "block_scale", "load_bias", "store_out", "lane_rank",
+                 "check_expert_call"):                       # called, not restated (scale_value is reached through block_scale)
         assert not re.search(r"^(?:__device__ __forceinline__|static(?: inline)?) [\w ]+ " + name + r"\(", src, flags=re.M), name
         assert re.search(r"\b" + name + r"(?:<\w+>)?\(", src) and name in shared, name
+    for name in ("transpose_blocks", "block_scale"):         # defined once in mx_decode.h, as tests/test_moe_host.py holds for the rest
+        assert len(re.findall(r"^__device__ __forceinline__ [\w ]+ " + name + r"\(", shared, flags=re.M)) == 1, name
+    # the transpose and the NaN-scale rule are mx_decode.h's text alone
+    assert "permlane32_swap" not in src and "kNaNScale" not in src and "scale_value" not in src
+    assert shared.count("__builtin_amdgcn_permlane32_swap") == 2 and shared.count("byte == (uint32_t)kNaNScale") == 2
     assert "_loader" in open(gn.__file__).read() and "CDLL" not in open(gn.__file__).read()
     assert f"#define MBNB_MOEGEMM_ROW_TILE {cases.R}" in open(HEADER).read() and re.search(r"constexpr int kNT = (\d+);", src).group(1) == str(cases.C // 16)
 
@@ -106,14 +112,40 @@ def _body(text, head):
     return " ".join(text[i + 1:j - 1].split())
 
 
-def test_the_restated_bodies_are_those_of_the_mlp_library():
-    mine, theirs = open(SOURCE).read(), open(os.path.join(CSRC, "moemlp_kernels.hip")).read()
+def test_the_epilogue_and_the_routed_sum_are_defined_once_for_both_routes():
+    """glu, the Glu exchange and store, k_routed_sum and its launch stand in csrc/mx_experts.h and nowhere else; the two kernel files
+    include it, call them and define none; the texts that fix the bits are what they were"""
+    shared = open(os.path.join(CSRC, "mx_experts.h")).read()
+    files = {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".h"))}
+    users = ("moemlp_kernels.hip", "moegemm_kernels.hip")
+    chain = "acc = __builtin_fmaf(load_bias(rw, rw_dtype, p), ws[p * N + n], acc);"
+    for text in ("float glu(", "void glu_store(", "void k_routed_sum(", "int launch_routed_sum(", "int check_glu_params(", "int check_workspace(",
+                 chain, "expf(-t)", "__shfl_xor(pre, 1)", "alpha = %g is not finite", "limit = %g is not positive", "the workspace is NULL or holds",
+                 "hipLaunchKernelGGL(k_routed_sum"):
+        assert [name for name, body in files.items() if text in body] == ["mx_experts.h"] and shared.count(text) == 1, text
+    family = "".join(body for body in files.values() if '#include "mx_decode.h"' in body) + files["mx_decode.h"]
+    assert len(re.findall(r"\bname16\(int", family)) == 1 and "name16(int" in files["mx_decode.h"] and '? "bf16" : "f16"' not in files["moe_kernels.hip"]
+    assert '#include "mx_decode.h"' in shared and [n for n, body in files.items() if '#include "mx_experts.h"' in body] == sorted(users)
     head = "__device__ __forceinline__ float glu(float g, float u, float alpha, float limit)"
-    assert _body(mine, head) == _body(theirs, head) and "expf(-t)" in _body(mine, head)
-    loop = "for (int a = 0; a < A; ++a)"
-    assert _body(mine, loop) == _body(theirs, loop) and "__builtin_fmaf(load_bias(rw, rw_dtype, p), ws[p * N + n], acc)" in _body(mine, loop)
-    whole = "void k_routed_sum("
-    assert _body(mine, whole) == _body(theirs, whole)
+    assert _body(shared, head) == ("g = g > limit ? limit : g; u = u > limit ? limit : (u < -limit ? -limit : u); const float t = alpha * g; "
+                                   "const float den = 1.0f + expf(-t); const float sig = 1.0f / den; const float gs = g * sig; "
+                                   "const float up = u + 1.0f; return up * gs;")
+    assert _body(shared, "for (int a = 0; a < A; ++a)") == ("const int64_t p = t * A + a; const int id = ids[p]; if (id < 0 || id >= E) continue; " + chain)
+    assert "static __global__ __launch_bounds__(kSumThreads) void k_routed_sum(" in shared and "constexpr int kSumThreads = 256;" in shared
+    store = _body(shared, "void glu_store(")
+    assert store.startswith("const float other = __shfl_xor(pre, 1); if (") and "row * (N / 2) + col / 2, glu(pre, other, alpha, limit)" in store
+    calls = lambda text, name: len(re.findall(r"\b" + name + r"\(", text))
+    for name in users:
+        src = files[name]
+        assert calls(src, "glu_store") == 1 == calls(src, "launch_routed_sum") == calls(src, "check_glu_params") == calls(src, "check_workspace"), name
+        assert calls(src, "glu") == 0 and "__shfl_xor(pre" not in src and "kSumThreads" not in src, name
+        assert "ERR_WORKSPACE == mbnb::mx::kErrWorkspace" in src, name
+        for helper in ("known_dtype", "ws_bytes", "name16"):  # the small host helpers too: called here, defined in the headers
+            assert not re.search(r"^[\w ]*\b" + helper + r"\(int", src, flags=re.M) and calls(src, helper) >= 1, (name, helper)
+    assert "static inline bool known_dtype(int d)" in shared and "static inline int64_t ws_bytes(int64_t P, int64_t N)" in shared
+    assert "constexpr int kErrWorkspace = -3;" in shared
+    # the kernels the other two decode libraries build stay what they were: neither includes this header (held above), so neither gets the kernel
+    assert "k_routed_sum" not in files["mx_kernels.hip"] and "k_routed_sum" not in files["moe_kernels.hip"] and "k_routed_sum" not in files["mx_decode.h"]
 
 
 def test_argument_errors_are_a_status_before_any_device_access():

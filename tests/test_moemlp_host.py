@@ -83,7 +83,8 @@ def test_the_makefile_the_build_and_the_source():
         assert re.search(r"__device__ __forceinline__ [\w ]+ " + name + r"\(", shared), name
         assert not re.search(r"__device__ __forceinline__ [\w ]+ " + name + r"\(", src), name
     # the decode tile, the pair list and the checks of an expert call are the header's too: this file only calls them
-    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers"):
+    for name in ("tile_walk", "tile_reduce", "list_pairs", "lane_rank", "check_expert_call", "check_expert_pointers", "transpose_blocks",
+                 "block_scale"):
         definition = re.compile(r"^(?:__device__ __forceinline__|static) [\w ]+ " + name + r"\(", flags=re.M)
         assert len(definition.findall(shared)) == 1 and not definition.search(src), name
     for inner in ("__builtin_amdgcn_permlane32_swap", "mfma16(", "decode8_16<"):
