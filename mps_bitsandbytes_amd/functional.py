@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _mx_native, _native, _router_native, _sparse_native, _train_native
+from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -2308,6 +2308,33 @@ def _experts_sum(what: str, grouped: bool, ops, plan=None) -> Tensor:
     return out
 
 
+def _experts_scaled(what: str, act: int, ops, plan=None) -> Tensor:
+    """The plain projection on libmbnb_moemx.so: the rows quantised to MX (one launch of the quantiser), then per cut of at most
+    MOE_GROUPED_MAX_PAIRS pairs one launch of k_mx_experts_scaled over the plan of that cut."""
+    x, w, s, ids, b, _, T, A, E, N, K, out_dtype, ocode = ops
+    out = torch.empty(T, A, N, dtype=out_dtype, device=x.device)
+    if T * A == 0:
+        return out
+    plans = _grouped_plans_of(what, plan, ids, T, A, E)
+    per_slot = int(x.dim() == 3)
+    codes, scales = quantize_mx(x.reshape(-1, K), "fp8" if act == _moemx_native.FP8 else "fp4")
+    codes, scales = codes.view(*x.shape[:-1], -1), scales.view(*x.shape[:-1], -1)
+    fn, bcode = _moemx_native.lib().mbnb_moemx_experts, 0 if b is None else _native.DTYPE_CODE[b.dtype]
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
+            _moemx_native.check(fn(ptr(codes[t0:t1]), ptr(scales[t0:t1]), act, t1 - t0, A, per_slot, K, ptr(w), ptr(s), E, N, ptr(ids[t0:t1]),
+                                   ptr(b), bcode, ptr(out[t0:t1]), ocode, *_plan_args(q), stream), what)
+    return out
+
+
+def _experts_act_format(what: str, act_format) -> Optional[int]:
+    """None for "none" (the activation stays in its dtype), else the MX element code of a quantised activation."""
+    if isinstance(act_format, str) and act_format == "none":
+        return None
+    return _mx_elem(act_format, what)
+
+
 def matmul_mxfp4_experts_grouped(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
                                  dtype: Optional[torch.dtype] = None, plan=None) -> Tensor:
     """
@@ -2322,6 +2349,24 @@ def matmul_mxfp4_experts_grouped(input: Tensor, weight: Tensor, weight_scales: T
     what = "matmul_mxfp4_experts_grouped"
     ops = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, None, dtype)
     return _experts_plain(what, True, ops, plan)
+
+
+def matmul_mxfp4_experts_scaled(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                                dtype: Optional[torch.dtype] = None, plan=None, act_format: str = "fp8") -> Tensor:
+    """
+    `matmul_mxfp4_experts_grouped` with an activation format: the same operands, checks, plan and cuts.
+    ``act_format="fp8"`` / ``"fp4"`` quantise the activation rows to MXFP8 / MXFP4 first (`quantize_mx`: T rows of a [T, K] input,
+    T * A of a [T, A, K] one) and run `k_mx_experts_scaled` of libmbnb_moemx.so over the plan: the block-scaled MFMA reads both
+    operands as they lie in memory.  A pair's bits are those of ``matmul_mxfp4(row, W[e], s[e], bias[e], act_format=act_format)``,
+    whatever else is in the call; a pair whose id is outside [0, E) gets a row of +0.0.  ``"none"`` is
+    `matmul_mxfp4_experts_grouped` itself; any other string is a ValueError.  Opt-in: no other function takes this route.
+    """
+    what = "matmul_mxfp4_experts_scaled"
+    act = _experts_act_format(what, act_format)
+    if act is None:
+        return matmul_mxfp4_experts_grouped(input, weight, weight_scales, expert_ids, bias, dtype, plan)
+    ops = _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, None, dtype)
+    return _experts_scaled(what, act, ops, plan)
 
 
 def matmul_mxfp4_experts_grouped_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,

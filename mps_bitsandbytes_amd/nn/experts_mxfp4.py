@@ -6,6 +6,9 @@ No counterpart in the reference.  Buffers `weight` uint8 [E, N, K / 2] (even k i
 `functional.matmul_mxfp4_experts`: one launch evaluates every (token, slot) pair against the expert `expert_ids[t, a]` names,
 the ids read on the device.  The routed sum over the slots and the activation between two projections are the
 caller's.  Inference only: an input or a bias that requires grad, with grad enabled, raises NotImplementedError.
+
+The attribute `act_format` = "fp8" / "fp4" (default "none"; `from_weights(..., act_format=...)` sets it) quantises the activation rows to MX and takes, at every pair count, the grouped GEMM on
+the block-scaled MFMA (`functional.matmul_mxfp4_experts_scaled`).
 """
 from typing import Optional
 
@@ -20,6 +23,7 @@ _BLOCK = 32
 
 class ExpertsMXFP4(QuantizedModule):
     _anchor = 'weight'
+    act_format = "none"        # "fp8" / "fp4": set by from_weights(act_format=...) or assigned on the module
 
     def __init__(self, num_experts: int, in_features: int, out_features: int, bias: bool = True, device=None,
                  compute_dtype: torch.dtype = torch.bfloat16):
@@ -39,11 +43,13 @@ class ExpertsMXFP4(QuantizedModule):
 
     def forward(self, x: Tensor, expert_ids: Tensor) -> Tensor:
         """x [T, K] (shared by a token's slots) or [T, A, K] (a row per slot), f16 / bf16; expert_ids [T, A] -> [T, A, N] in x's dtype."""
+        if self.act_format != "none":
+            return F.matmul_mxfp4_experts_scaled(x, self.weight, self.weight_scales, expert_ids, self.bias, act_format=self.act_format)
         return F.matmul_mxfp4_experts(x, self.weight, self.weight_scales, expert_ids, self.bias)
 
     @classmethod
     def from_weights(cls, weight: Tensor, bias: Optional[Tensor] = None, device=None,
-                     compute_dtype: Optional[torch.dtype] = None) -> 'ExpertsMXFP4':
+                     compute_dtype: Optional[torch.dtype] = None, act_format: str = "none") -> 'ExpertsMXFP4':
         """Quantise expert weights [E, N, K] (and copy a bias [E, N]) on `device` with the HIP quantiser, expert by expert row."""
         if weight.dim() != 3:
             raise ValueError(f"ExpertsMXFP4.from_weights: weight must be [E, N, K], got {tuple(weight.shape)}")
@@ -53,7 +59,10 @@ class ExpertsMXFP4(QuantizedModule):
         device = source_device(weight, device)
         wdtype = weight.dtype
         cd = compute_dtype if compute_dtype is not None else (wdtype if wdtype in (torch.float16, torch.bfloat16) else torch.bfloat16)
+        if act_format not in ("none", "fp8", "fp4"):
+            raise ValueError(f"ExpertsMXFP4.from_weights: unknown act_format {act_format!r} (supported: 'none', 'fp8', 'fp4')")
         layer = cls(E, K, N, bias=bias is not None, device=device, compute_dtype=cd)
+        layer.act_format = act_format
         codes, scales = F.quantize_mx(weight.detach().to(device).reshape(E * N, K), "fp4")
         layer.weight.copy_(codes.view(E, N, K // 2))
         layer.weight_scales.copy_(scales.view(E, N, K // _BLOCK))
