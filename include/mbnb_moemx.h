@@ -26,7 +26,8 @@
  * expert e at column n.  A pair whose id is outside [0, E) gets a row of +0.0.
  *
  * THE PLAN is mbnb_moegemm_plan's, built from the same ids, P and E (mbnb_moegemm.h; this library reads it, it does not build
- * it), as int32 words in this order, R = MBNB_MOEMX_ROW_TILE = MBNB_MOEGEMM_ROW_TILE, max_tiles = min(E, P) + P / R:
+ * it; both go through ONE text of the layout, csrc/mx_plan.h), as int32 words in this order, R = MBNB_MOEMX_ROW_TILE =
+ * MBNB_MOEGEMM_ROW_TILE, max_tiles = min(E, P) + P / R:
  *   counts[E]            (not read here)
  *   n_tiles, n_listed    the entries of the tile table in use, and the pairs with an id in [0, E)
  *   tiles[max_tiles][3]  (expert, first index into sorted, rows <= R), the entries past n_tiles unwritten

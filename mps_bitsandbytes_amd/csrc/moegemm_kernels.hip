@@ -18,10 +18,14 @@
 #include "host.h"
 #include "mx_decode.h"
 #include "mx_experts.h"
+#include "mx_plan.h"
 
 static_assert(MBNB_MOEGEMM_F16 == mbnb::kF16 && MBNB_MOEGEMM_BF16 == mbnb::kBF16 && MBNB_MOEGEMM_F32 == mbnb::kF32, "host.h's dtype codes");
 static_assert(MBNB_MOEGEMM_ERR_ARG == mbnb::mx::kErrArg && MBNB_MOEGEMM_ERR_SHAPE == mbnb::mx::kErrShape, "mx_decode.h's statuses");
-static_assert(MBNB_MOEGEMM_ERR_WORKSPACE == mbnb::mx::kErrWorkspace, "mx_experts.h's status");
+static_assert(MBNB_MOEGEMM_ERR_WORKSPACE == mbnb::mx::kErrWorkspace && MBNB_MOEGEMM_ERR_WORKSPACE == mbnb::mx::kErrPlan, "mx_experts.h's and mx_plan.h's status");
+static_assert(MBNB_MOEGEMM_ROW_TILE == mbnb::mx::kPlanRowTile && MBNB_MOEGEMM_MAX_PAIRS == mbnb::mx::kPlanMaxPairs &&
+                  MBNB_MOEGEMM_MAX_EXPERTS == mbnb::mx::kPlanMaxExperts,
+              "mx_plan.h's tile and limits");
 static_assert(MBNB_MOEGEMM_ROW_TILE % 16 == 0 && MBNB_MOEGEMM_ROW_TILE % 32 == 0, "whole A fragments, and 8 waves share the 4 R / 16 sums of a round");
 static_assert(MBNB_MOEGEMM_MAX_PAIRS >= 65536 && (int64_t)MBNB_MOEGEMM_MAX_PAIRS * 4 < INT32_MAX, "a pair index and a list offset are an int");
 
@@ -42,7 +46,6 @@ using mbnb::mx::BlockScale;
 using mbnb::mx::load_bias;
 using mbnb::mx::store_out;
 using mbnb::mx::lane_rank;
-using mbnb::mx::check_expert_call;
 using mbnb::mx::check_expert_nulls;
 using mbnb::mx::check_expert_alignment;
 using mbnb::mx::name16;
@@ -52,6 +55,13 @@ using mbnb::mx::ws_bytes;
 using mbnb::mx::check_glu_params;
 using mbnb::mx::check_workspace;
 using mbnb::mx::launch_routed_sum;
+// the plan's layout and size, and the shape checks of a grouped call: mx_plan.h, shared with moemx_kernels.hip
+using mbnb::mx::max_tiles_of;
+using mbnb::mx::plan_bytes_of;
+using mbnb::mx::plan_of;
+using mbnb::mx::PlanTile;
+using mbnb::mx::check_grouped_call;
+using mbnb::mx::check_plan;
 
 constexpr int kMaxExperts = MBNB_MOEGEMM_MAX_EXPERTS;
 constexpr int kMaxGroupedPairs = MBNB_MOEGEMM_MAX_PAIRS;
@@ -67,11 +77,7 @@ struct Plain { static constexpr bool kGlu = false, kZeros = true; };
 struct Glu { static constexpr bool kGlu = true, kZeros = true; };
 struct PlainF32 { static constexpr bool kGlu = false, kZeros = false; };
 
-// ---------------------------------------------------------------- the plan
-// int32 words: counts[E], n_tiles, n_listed, tiles[max_tiles][3], sorted[P]
-__host__ __device__ inline int64_t max_tiles_of(int64_t P, int64_t E) { return (E < P ? E : P) + P / kRowTile; }
-int64_t plan_words(int64_t P, int64_t E) { return E + 2 + 3 * max_tiles_of(P, E) + P; }
-
+// ---------------------------------------------------------------- the plan (its words: mx_plan.h)
 // workgroup e: counts[e]
 __global__ __launch_bounds__(kPlanThreads) void k_plan_count(const int32_t *__restrict__ ids, int P, int32_t *__restrict__ plan) {
     __shared__ int part[kPlanWaves];
@@ -119,19 +125,20 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_fill(const int32_t *__res
         off += sums[0][w];
         toff += sums[1][w];
     }
-    int32_t *tiles = plan + E + 2, *sorted = tiles + 3 * (int64_t)max_tiles;
+    const auto pl = plan_of(plan, E, max_tiles);
+    int32_t *sorted = pl.sorted;
     if (b == E) {
         if (tid == 0) {
-            plan[E] = toff;
-            plan[E + 1] = off;
+            *pl.n_tiles = toff;
+            *pl.n_listed = off;
         }
     } else {
         const int count = plan[b];
         for (int t = tid; t * kRowTile < count; t += kPlanThreads) {
             const int left = count - t * kRowTile;
-            tiles[3 * (toff + t)] = b;
-            tiles[3 * (toff + t) + 1] = off + t * kRowTile;
-            tiles[3 * (toff + t) + 2] = left < kRowTile ? left : kRowTile;
+            pl.tiles[3 * (toff + t)] = b;
+            pl.tiles[3 * (toff + t) + 1] = off + t * kRowTile;
+            pl.tiles[3 * (toff + t) + 2] = left < kRowTile ? left : kRowTile;
         }
     }
     int base = off;
@@ -191,8 +198,9 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x / col_tiles;
     const int64_t n0 = (int64_t)(blockIdx.x % col_tiles) * kColTile;
-    const int32_t *tiles = plan + E + 2, *sorted = tiles + 3 * (int64_t)max_tiles;
-    const int n_tiles = plan[E], n_listed = plan[E + 1];
+    const auto pl = plan_of(plan, E, max_tiles);
+    const int32_t *sorted = pl.sorted;
+    const int n_tiles = *pl.n_tiles, n_listed = *pl.n_listed;
     const int64_t width = EPI::kGlu ? N / 2 : N;            // of a row of out
 
     if (EPI::kZeros) {                                      // the rows of +0.0 of the out-of-range pairs, this column tile's outputs
@@ -202,7 +210,8 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
             if (col < width) store_out(out, out_dtype, (int64_t)sorted[i] * width + col, 0.0f);
     }
     if (tile >= n_tiles) return;                            // uniform: no weight byte is touched, no barrier was met
-    const int e = tiles[3 * tile], first = tiles[3 * tile + 1], rows = tiles[3 * tile + 2];
+    const PlanTile entry = pl.tile(tile);
+    const int e = entry.e, first = entry.first, rows = entry.rows;
 
     const int64_t KB = K / 32, ldw = K / 2, last = KB - 1, steps = (KB + 3) / 4;
     const uint8_t *w_row[kNT], *s_row[kNT];
@@ -311,34 +320,6 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_grouped(const T *__rest
 }
 
 // ---------------------------------------------------------------- host side
-int64_t plan_bytes_of(int64_t P, int64_t E) { return mbnb::round256(plan_words(P, E) * 4); }
-
-// The shape checks of a projection call: mx_decode.h's for everything but the pairs (asked with none, its limit being the decode
-// launches'), then the pairs of this library, the outputs and the grid.
-int check_grouped_call(const char *what, int64_t T, int64_t A, int64_t K, int row_dtype, int64_t E, int64_t N, int bias_dtype, bool has_bias,
-                       int out_dtype) {
-    if (const int st = check_expert_call(what, 0, 0, K, row_dtype, E, N, bias_dtype, has_bias, out_dtype, kMaxExperts, true)) return st;
-    if (T < 0 || A < 0) return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: T = %lld, A = %lld", what, (long long)T, (long long)A);
-    if (T > 0 && A > kMaxGroupedPairs / T)
-        return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: T x A = %lld x %lld pairs, at most %d in one launch", what, (long long)T, (long long)A,
-                    kMaxGroupedPairs);
-    const int64_t P = T * A;
-    if (P > 0 && N > mbnb::kMaxElems / P)
-        return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: %lld x %lld outputs exceed one launch", what, (long long)P, (long long)N);
-    const int64_t col_tiles = (N + kColTile - 1) / kColTile;   // under the limits above the grid stays below 2^31: the guard of the launch's cast
-    if (P > 0 && col_tiles > INT32_MAX / max_tiles_of(P, E))
-        return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: %lld x %lld workgroups exceed one launch", what, (long long)col_tiles,
-                    (long long)max_tiles_of(P, E));
-    return 0;
-}
-
-int check_plan(const char *what, const void *plan, int64_t plan_bytes, int64_t P, int64_t E) {
-    if (!plan || plan_bytes < plan_bytes_of(P, E))
-        return fail(MBNB_MOEGEMM_ERR_WORKSPACE, "%s: the plan is NULL or holds %lld bytes, %lld needed", what, (long long)plan_bytes,
-                    (long long)plan_bytes_of(P, E));
-    return 0;
-}
-
 template <typename T, typename EPI>
 int launch_grouped(const void *x, const void *W, const void *Ws, const void *plan, int64_t P, int64_t x_div, int64_t E, int64_t N, int64_t K,
                    const void *bias, int bias_dtype, void *out, int out_dtype, float alpha, float limit, hipStream_t s) {
@@ -380,7 +361,7 @@ int mbnb_moegemm_plan(const int32_t *ids, int64_t P, int64_t E, void *plan, int6
     if (P == 0) return 0;
     const std::initializer_list<mbnb::mx::Operand> operands = {{"ids", ids, 4}, {"plan", plan, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (const int st = check_plan(what, plan, plan_bytes, P, E)) return st;
+    if (const int st = check_plan(what, plan, plan_bytes, P, E, "is NULL or holds")) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_plan_count, dim3((unsigned)E), dim3(kPlanThreads), 0, s, ids, (int)P, (int32_t *)plan);
@@ -396,14 +377,14 @@ int mbnb_moegemm_experts(const void *x, int64_t T, int64_t A, int x_per_slot, in
                          int64_t E, int64_t N, const int32_t *ids, const void *bias, int bias_dtype, void *out, int out_dtype, const void *plan,
                          int64_t plan_bytes, void *stream) {
     const char *const what = "mbnb_moegemm_experts";
-    if (const int st = check_grouped_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype)) return st;
+    if (const int st = check_grouped_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype, kColTile)) return st;
     const int64_t P = T * A;
     if (P == 0) return 0;
     const std::initializer_list<mbnb::mx::Operand> operands = {{"x", x, 16}, {"w_codes", w_codes, 16}, {"w_scales", w_scales, 1}, {"ids", ids, 4},
                                                                {"out", out, mbnb::esize(out_dtype)}, {"bias", bias, mbnb::esize(bias_dtype), true},
                                                                {"plan", plan, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (const int st = check_plan(what, plan, plan_bytes, P, E)) return st;
+    if (const int st = check_plan(what, plan, plan_bytes, P, E, "is NULL or holds")) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     const int st = launch_by_dtype<Plain>(x_dtype, x, w_codes, w_scales, plan, P, x_per_slot ? 1 : A, E, N, K, bias, bias_dtype, out, out_dtype, 0.0f,
                                           0.0f, (hipStream_t)stream);
@@ -419,7 +400,7 @@ int mbnb_moegemm_gate_up_glu(const void *x, int64_t T, int64_t A, int64_t K, int
     const char *const what = "mbnb_moegemm_gate_up_glu";
     if (I <= 0 || I > mbnb::kMaxElems / 2) return fail(MBNB_MOEGEMM_ERR_SHAPE, "%s: I = %lld", what, (long long)I);
     const int64_t N = 2 * I;
-    if (const int st = check_grouped_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype)) return st;
+    if (const int st = check_grouped_call(what, T, A, K, x_dtype, E, N, bias_dtype, bias != nullptr, out_dtype, kColTile)) return st;
     if (const int st = check_glu_params(what, alpha, limit)) return st;
     const int64_t P = T * A;
     if (P == 0) return 0;
@@ -427,7 +408,7 @@ int mbnb_moegemm_gate_up_glu(const void *x, int64_t T, int64_t A, int64_t K, int
                                                                {"out", out, mbnb::esize(out_dtype)}, {"bias", bias, mbnb::esize(bias_dtype), true},
                                                                {"plan", plan, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (const int st = check_plan(what, plan, plan_bytes, P, E)) return st;
+    if (const int st = check_plan(what, plan, plan_bytes, P, E, "is NULL or holds")) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     const int st = launch_by_dtype<Glu>(x_dtype, x, w_codes, w_scales, plan, P, A, E, N, K, bias, bias_dtype, out, out_dtype, alpha, limit,
                                         (hipStream_t)stream);
@@ -449,7 +430,7 @@ int mbnb_moegemm_down_sum(const void *h, int64_t T, int64_t A, int64_t K, int h_
                           int64_t N, const int32_t *ids, const void *bias, int bias_dtype, const void *rw, int rw_dtype, void *out, int out_dtype,
                           void *workspace, int64_t workspace_bytes, const void *plan, int64_t plan_bytes, void *stream) {
     const char *const what = "mbnb_moegemm_down_sum";
-    if (const int st = check_grouped_call(what, T, A, K, h_dtype, E, N, bias_dtype, bias != nullptr, out_dtype)) return st;
+    if (const int st = check_grouped_call(what, T, A, K, h_dtype, E, N, bias_dtype, bias != nullptr, out_dtype, kColTile)) return st;
     if (!known_dtype(rw_dtype)) return fail(MBNB_MOEGEMM_ERR_ARG, "%s: unknown dtype (rw %d)", what, rw_dtype);
     const int64_t P = T * A;
     if (P == 0) return 0;
@@ -459,7 +440,7 @@ int mbnb_moegemm_down_sum(const void *h, int64_t T, int64_t A, int64_t K, int h_
                                                                {"plan", plan, 16, true}};
     if (const int st = check_expert_nulls(what, operands)) return st;
     if (const int st = check_workspace(what, workspace, workspace_bytes, P, N)) return st;
-    if (const int st = check_plan(what, plan, plan_bytes, P, E)) return st;
+    if (const int st = check_plan(what, plan, plan_bytes, P, E, "is NULL or holds")) return st;
     if (const int st = check_expert_alignment(what, operands)) return st;
     hipStream_t s = (hipStream_t)stream;
     int st = launch_by_dtype<PlainF32>(h_dtype, h, w_codes, w_scales, plan, P, 1, E, N, K, bias, bias_dtype, workspace, MBNB_MOEGEMM_F32, 0.0f, 0.0f, s);

@@ -13,9 +13,15 @@
 #include "../../include/mbnb_moemx.h"
 #include "host.h"
 #include "mx_decode.h"
+#include "mx_plan.h"
+#include "mx_scaled.h"
 
 static_assert(MBNB_MOEMX_F16 == mbnb::kF16 && MBNB_MOEMX_BF16 == mbnb::kBF16 && MBNB_MOEMX_F32 == mbnb::kF32, "host.h's dtype codes");
 static_assert(MBNB_MOEMX_ERR_ARG == mbnb::mx::kErrArg && MBNB_MOEMX_ERR_SHAPE == mbnb::mx::kErrShape, "mx_decode.h's statuses");
+static_assert(MBNB_MOEMX_ERR_WORKSPACE == mbnb::mx::kErrPlan, "mx_plan.h's status");
+static_assert(MBNB_MOEMX_ROW_TILE == mbnb::mx::kPlanRowTile && MBNB_MOEMX_MAX_PAIRS == mbnb::mx::kPlanMaxPairs &&
+                  MBNB_MOEMX_MAX_EXPERTS == mbnb::mx::kPlanMaxExperts,
+              "mx_plan.h's tile and limits");
 
 namespace {
 
@@ -27,44 +33,39 @@ using mbnb::mx::v4i;
 using mbnb::mx::kNaNScale;
 using mbnb::mx::kOneScale;
 using mbnb::mx::load_bias;
-using mbnb::mx::check_expert_call;
 using mbnb::mx::check_expert_nulls;
 using mbnb::mx::check_expert_alignment;
+// the plan's layout and size, and the shape checks of a grouped call: mx_plan.h, shared with moegemm_kernels.hip
+using mbnb::mx::max_tiles_of;
+using mbnb::mx::plan_of;
+using mbnb::mx::PlanTile;
+using mbnb::mx::check_grouped_call;
+using mbnb::mx::check_plan;
+// the stage, the LDS-DMA, the fold of a NaN mask, the scaled MFMA and the epilogue value: mx_scaled.h, shared with k_gemm_mx
+using mbnb::mx::v8i;
+using mbnb::mx::ScaledStage;
+using mbnb::mx::dma16;
+using mbnb::mx::fold16;
+using mbnb::mx::scaled_mfma;
+using mbnb::mx::scaled_value;
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
-constexpr int kMaxExperts = MBNB_MOEMX_MAX_EXPERTS;
-constexpr int kMaxGroupedPairs = MBNB_MOEMX_MAX_PAIRS;
 constexpr int kRowTile = MBNB_MOEMX_ROW_TILE;            // R of the plan: listed pairs of a workgroup
 constexpr int kColTile = MBNB_MOEMX_COL_TILE;            // weight rows of a workgroup
 constexpr int KS = MBNB_MOEMX_K_STEP;
-constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kThreads = mbnb::mx::kScaledThreads, kWaves = kThreads / 64;
 constexpr int kStages = 2;                               // LDS stages: K-steps t and t + 1
-static_assert(kRowTile == 64 && kColTile == 64 * kWaves && KS == 128, "the wave grid and the chunk maps below are written for 64 x 256 x 128");
-static_assert((int64_t)kMaxGroupedPairs * 4 < INT32_MAX, "a pair index and a list offset are an int");
-
-// the plan of mbnb_moegemm.h, read here: counts[E], n_tiles, n_listed, tiles[max_tiles][3], sorted[P]
-__host__ __device__ inline int64_t max_tiles_of(int64_t P, int64_t E) { return (E < P ? E : P) + P / kRowTile; }
-int64_t plan_bytes_of(int64_t P, int64_t E) { return mbnb::round256((E + 2 + 3 * max_tiles_of(P, E) + P) * 4); }
+static_assert(kRowTile == 64 && kColTile == 64 * kWaves && KS == mbnb::mx::kScaledKStep,
+              "the wave grid and the chunk maps below are written for 64 x 256 x 128");
+static_assert((int64_t)MBNB_MOEMX_MAX_PAIRS * 4 < INT32_MAX, "a pair index and a list offset are an int");
 
 // s_waitcnt vmcnt(n) alone, the other counters left at their maxima (gfx9 encoding: vmcnt in bits 3:0 and 15:14)
 constexpr int vmcnt_only(int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); }
 
-__device__ __forceinline__ void dma16(const uint8_t *src, uint8_t *wave_dst) {     // 64 lanes x 16 bytes, lane l to wave_dst + 16 l
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)wave_dst, 16, 0,
-                                     0);
-}
-
-// Workgroup (tile, column tile).  The operand map of the instruction is DESIGN.md §25's: lane l = (g = l >> 4, fr = l & 15)
-// holds row (A) / column (B) fr; fp4: the k block g as 16 bytes; fp8: registers 0..3 the 16 k from 16 g, registers 4..7 the 16 k
-// from 64 + 16 g; scale register byte 0: the byte of k block g.  D: column fr, rows 4 g + r.
-//
-// LDS image of a stage, in 16-byte chunks: the activation tile [half][pair r][g] (fp4: one half; fp8: chunk [h][r][g] = the 16 k
-// from 64 h + 16 g), then the weight tile [column c][g].  Thread tid fetches chunk i * 256 + tid of an image: pair / column
-// (tid >> 2) (+ 64 i for the weight), g = tid & 3, so a wave's DMA writes 64 consecutive chunks and reads 16 rows x 64 bytes, and a
-// fragment read -- lane l takes chunk [row0 + fr][g] -- is 1 KiB of consecutive LDS.  Every load is unconditional, from a clamped
-// (valid) address: a pair past the tile's count reads the tile's first pair, a column past N weight row N - 1, a k past K the
-// row's first bytes; all three become zeros in registers with the scale 2^0, and nothing past an edge is stored.
+// Workgroup (tile, column tile); the operand map of the instruction and the LDS image of a stage are mx_scaled.h's.  Thread tid
+// fetches chunk i * 256 + tid of an image: pair / column (tid >> 2) (+ 64 i for the weight), g = tid & 3, so a wave's DMA writes
+// 64 consecutive chunks and reads 16 rows x 64 bytes.  Every load is unconditional, from a clamped (valid) address: a pair past
+// the tile's count reads the tile's first pair, a column past N weight row N - 1, a k past K the row's first bytes; all three
+// become zeros in registers with the scale 2^0, and nothing past an edge is stored.
 template <int AELEM, typename TOUT>
 __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *__restrict__ X, const uint8_t *__restrict__ Xs,
                                                                 const uint8_t *__restrict__ W, const uint8_t *__restrict__ Ws,
@@ -72,11 +73,9 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
                                                                 const void *__restrict__ bias, int bias_dtype, TOUT *__restrict__ out,
                                                                 int col_tiles, int max_tiles) {
     constexpr bool A8 = AELEM == MBNB_MOEMX_FP8;
-    constexpr int AH = A8 ? 2 : 1;                           // 16-byte halves of an activation block
-    constexpr int A_BYTES = kRowTile * 4 * AH * 16, B_BYTES = kColTile * 4 * 16, STAGE = A_BYTES + B_BYTES;
-    constexpr int NA = A_BYTES / 16 / kThreads, NB = B_BYTES / 16 / kThreads;   // LDS-DMA instructions per thread and stage
-    constexpr int CBSZ = A8 ? 0 : 4, BLGP = 4;
-    static_assert(NA == AH && NB == 4, "the chunk maps below");
+    using S = ScaledStage<A8, kRowTile, kColTile>;
+    constexpr int A_BYTES = S::A_BYTES, STAGE = S::STAGE, NA = S::NA, NB = S::NB;
+    static_assert(NA == S::AH && NB == 4, "the chunk maps below");
     __shared__ __attribute__((aligned(16))) uint8_t smem[kStages * STAGE];
     __shared__ int pairs[kRowTile];
 
@@ -84,8 +83,9 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x / col_tiles;
     const int64_t n0 = (int64_t)(blockIdx.x % col_tiles) * kColTile;
-    const int32_t *tiles = plan + E + 2, *sorted = tiles + 3 * (int64_t)max_tiles;
-    const int n_tiles = plan[E], n_listed = plan[E + 1];
+    const auto pl = plan_of(plan, E, max_tiles);
+    const int32_t *sorted = pl.sorted;
+    const int n_tiles = *pl.n_tiles, n_listed = *pl.n_listed;
 
     {   // the rows of +0.0 of the out-of-range pairs, this column tile's outputs: a grid-stride loop over the tile index
         const int64_t col = n0 + tid;
@@ -93,7 +93,8 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
             if (col < N) out[(int64_t)sorted[i] * N + col] = (TOUT)0.0f;
     }
     if (tile >= n_tiles) return;                             // uniform: no weight byte is touched, no barrier was met
-    const int e = tiles[3 * tile], first = tiles[3 * tile + 1], rows = tiles[3 * tile + 2];
+    const PlanTile entry = pl.tile(tile);
+    const int e = entry.e, first = entry.first, rows = entry.rows;
     if (tid < kRowTile) pairs[tid] = sorted[first + (tid < rows ? tid : 0)];
     __syncthreads();
 
@@ -154,8 +155,6 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
             sb[i] = in && b_live[i] ? rb[i] : kOneScale;
         }
     };
-    // bit q of the mask: row / column q of the 16 x 16 tile has a NaN block (a lane holds row fr's scale, not its outputs' rows)
-    auto fold16 = [](uint64_t b) { return (uint32_t)((b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xFFFFu); };
 
     v4f acc[4][4];
 #pragma unroll
@@ -217,8 +216,7 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[i], bf[j], acc[i][j], CBSZ, BLGP, 0, sa[i], 0, sb[j]);
+            for (int j = 0; j < 4; ++j) acc[i][j] = scaled_mfma<S::CBSZ, S::BLGP>(af[i], bf[j], acc[i][j], sa[i], sb[j]);
     }
 
     // epilogue: + bias in f32, NaN rows and columns, one rounding, guarded stores to the rows of the listed pairs
@@ -234,9 +232,7 @@ __global__ __launch_bounds__(kThreads) void k_mx_experts_scaled(const uint8_t *_
             for (int r = 0; r < 4; ++r) {
                 const int row = 16 * i + 4 * g + r;
                 if (row >= rows) continue;
-                float v = acc[i][j][r] + b;
-                if (col_nan || ((a_nan[i] >> (4 * g + r)) & 1u)) v = __uint_as_float(0x7FC00000u);
-                out[(int64_t)pairs[row] * N + col] = (TOUT)v;
+                out[(int64_t)pairs[row] * N + col] = (TOUT)scaled_value(acc[i][j][r], b, col_nan, a_nan[i], 4 * g + r);
             }
     }
 }
@@ -270,25 +266,15 @@ int mbnb_moemx_experts(const void *x_codes, const void *x_scales, int act_elem, 
                        const void *plan, int64_t plan_bytes, void *stream) {
     const char *const what = "mbnb_moemx_experts";
     if (act_elem != MBNB_MOEMX_FP4 && act_elem != MBNB_MOEMX_FP8) return fail(MBNB_MOEMX_ERR_ARG, "%s: unknown act_elem %d", what, act_elem);
-    // mx_decode.h's checks of everything but the rows (which are codes here: asked as 16-bit) and the pairs (asked with none)
-    if (const int st = check_expert_call(what, 0, 0, K, MBNB_MOEMX_BF16, E, N, bias_dtype, bias != nullptr, out_dtype, kMaxExperts, true)) return st;
-    if (T < 0 || A < 0) return fail(MBNB_MOEMX_ERR_SHAPE, "%s: T = %lld, A = %lld", what, (long long)T, (long long)A);
-    if (T > 0 && A > kMaxGroupedPairs / T)
-        return fail(MBNB_MOEMX_ERR_SHAPE, "%s: T x A = %lld x %lld pairs, at most %d in one launch", what, (long long)T, (long long)A,
-                    kMaxGroupedPairs);
+    // mx_plan.h's shape checks; the rows are codes here, asked as 16-bit
+    if (const int st = check_grouped_call(what, T, A, K, MBNB_MOEMX_BF16, E, N, bias_dtype, bias != nullptr, out_dtype, kColTile)) return st;
     const int64_t P = T * A;
-    if (P > 0 && N > mbnb::kMaxElems / P)
-        return fail(MBNB_MOEMX_ERR_SHAPE, "%s: %lld x %lld outputs exceed one launch", what, (long long)P, (long long)N);
     if (P == 0) return 0;
-    const int64_t col_tiles = (N + kColTile - 1) / kColTile;    // the guard of the launch's cast
-    if (col_tiles > INT32_MAX / max_tiles_of(P, E))
-        return fail(MBNB_MOEMX_ERR_SHAPE, "%s: %lld x %lld workgroups exceed one launch", what, (long long)col_tiles, (long long)max_tiles_of(P, E));
     const std::initializer_list<mbnb::mx::Operand> operands = {{"x_codes", x_codes, 16}, {"x_scales", x_scales, 1}, {"w_codes", w_codes, 16},
                                                                {"w_scales", w_scales, 1}, {"ids", ids, 4}, {"out", out, mbnb::esize(out_dtype)},
                                                                {"bias", bias, mbnb::esize(bias_dtype), true}, {"plan", plan, 16}};
     if (const int st = check_expert_nulls(what, operands)) return st;
-    if (plan_bytes < plan_bytes_of(P, E))
-        return fail(MBNB_MOEMX_ERR_WORKSPACE, "%s: the plan holds %lld bytes, %lld needed", what, (long long)plan_bytes, (long long)plan_bytes_of(P, E));
+    if (const int st = check_plan(what, plan, plan_bytes, P, E, "holds")) return st;     // a NULL plan was refused among the pointers
     if (const int st = check_expert_alignment(what, operands)) return st;
     const int64_t x_div = x_per_slot ? 1 : A;
     hipStream_t s = (hipStream_t)stream;

@@ -1,6 +1,8 @@
 // mx_decode.h — what the four MXFP4 decode libraries share: mx_kernels.hip (k_mx_decode,
 // k_mx_decode_mfma), moe_kernels.hip (k_mx_experts), moemlp_kernels.hip (k_mx_experts_rt) and moegemm_kernels.hip
-// (k_mx_experts_grouped); the last two through mx_experts.h, which adds what only the expert MLP shares.
+// (k_mx_experts_grouped); the last two through mx_experts.h, which adds what only the expert MLP shares.  Two more headers stand on
+// this one (§35): mx_scaled.h, the block-scaled MFMA tile of k_gemm_mx (mx_kernels.hip) and k_mx_experts_scaled
+// (moemx_kernels.hip), and mx_plan.h, the plan of a grouped call and its shape checks (moegemm_kernels.hip, moemx_kernels.hip).
 //
 //   device   the E8M0 scale, the byte-table decode of 8 E2M1 codes to 8 values of the activation's 16-bit type, the MFMA of one MX
 //            block, the bias load and output store by dtype code; transpose_blocks (the 4 x 4 transpose of a k-step's weight

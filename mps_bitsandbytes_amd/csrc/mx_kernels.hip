@@ -13,6 +13,7 @@
 #include "../../include/mbnb_mx.h"
 #include "host.h"
 #include "mx_decode.h"
+#include "mx_scaled.h"
 
 static_assert(MBNB_MX_F16 == mbnb::kF16 && MBNB_MX_BF16 == mbnb::kBF16 && MBNB_MX_F32 == mbnb::kF32, "host.h's dtype codes");
 
@@ -34,10 +35,16 @@ using mbnb::mx::TileLds;
 using mbnb::mx::TileSums;
 using mbnb::mx::tile_walk;
 using mbnb::mx::tile_reduce;
+// the stage, the LDS-DMA, the fold of a NaN mask, the scaled MFMA and the epilogue value of k_gemm_mx: mx_scaled.h, shared with
+// k_mx_experts_scaled (moemx_kernels.hip)
+using mbnb::mx::v8i;
+using mbnb::mx::ScaledStage;
+using mbnb::mx::dma16;
+using mbnb::mx::fold16;
+using mbnb::mx::scaled_mfma;
+using mbnb::mx::scaled_value;
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
-constexpr int kThreads = 256;          // every launch: 4 waves
+constexpr int kThreads = mbnb::mx::kScaledThreads;    // every launch: 4 waves
 
 // ---------------------------------------------------------------- the element formats
 // |a| -> E2M1 code 0..7 (0, .5, 1, 1.5, 2, 3, 4, 6), nearest, ties to the even code, everything above 5 to 6
@@ -185,10 +192,8 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
                                                       int64_t K, const void *__restrict__ bias, int bias_dtype, TO *__restrict__ out,
                                                       int tiles_m) {
     constexpr bool A8 = AELEM == MBNB_MX_FP8;
-    constexpr int AH = A8 ? 2 : 1;                           // 16-byte halves of an activation block
-    constexpr int A_BYTES = TM * 4 * AH * 16, B_BYTES = TN * 4 * 16, STAGE = A_BYTES + B_BYTES;
-    constexpr int NA = A_BYTES / 16 / kThreads, NB = B_BYTES / 16 / kThreads;   // LDS-DMA instructions per thread and stage
-    constexpr int CBSZ = A8 ? 0 : 4, BLGP = 4;
+    using S = ScaledStage<A8, TM, TN>;
+    constexpr int A_BYTES = S::A_BYTES, STAGE = S::STAGE, NA = S::NA, NB = S::NB;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * STAGE];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 15, g = lane >> 4;
@@ -217,16 +222,12 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const uint8_t *p = a_src[i] && k0 + a_k[i] < K ? a_src[i] + (A8 ? k0 : k0 >> 1) : A;
-            auto gp = (const __attribute__((address_space(1))) void *)p;
-            auto lp = (__attribute__((address_space(3))) void *)(smem + s * STAGE + (i * kThreads + wave * 64) * 16);
-            __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+            dma16(p, smem + s * STAGE + (i * kThreads + wave * 64) * 16);
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const uint8_t *p = b_src[i] && k0 + b_k[i] < K ? b_src[i] + (k0 >> 1) : W;
-            auto gp = (const __attribute__((address_space(1))) void *)p;
-            auto lp = (__attribute__((address_space(3))) void *)(smem + s * STAGE + A_BYTES + (i * kThreads + wave * 64) * 16);
-            __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+            dma16(p, smem + s * STAGE + A_BYTES + (i * kThreads + wave * 64) * 16);
         }
     };
 
@@ -246,8 +247,6 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
             sb[i] = ws_row[i] && kb < KB ? (int)ws_row[i][kb] : kOneScale;
         }
     };
-    // bit q of the mask: row / column q of the 16 x 16 tile has a NaN block (a lane holds row l & 15's scale, not its outputs' rows)
-    auto fold16 = [](uint64_t b) { return (uint32_t)((b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xFFFFu); };
 
     v4f acc[4][4];
 #pragma unroll
@@ -305,8 +304,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[i], bf[j], acc[i][j], CBSZ, BLGP, 0, sa[i], 0, sb[j]);
+            for (int j = 0; j < 4; ++j) acc[i][j] = scaled_mfma<S::CBSZ, S::BLGP>(af[i], bf[j], acc[i][j], sa[i], sb[j]);
     }
 
     // epilogue: + bias in f32, NaN rows and columns, one rounding, guarded stores
@@ -322,9 +320,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_mx(const uint8_t *__restrict_
             for (int r = 0; r < 4; ++r) {
                 const int64_t row = m0 + wm * 64 + i * 16 + 4 * g + r;
                 if (row >= M) continue;
-                float v = acc[i][j][r] + b;
-                if (col_nan || ((a_nan[i] >> (4 * g + r)) & 1u)) v = __uint_as_float(0x7FC00000u);
-                out[row * N + col] = (TO)v;
+                out[row * N + col] = (TO)scaled_value(acc[i][j][r], b, col_nan, a_nan[i], 4 * g + r);
             }
     }
 }

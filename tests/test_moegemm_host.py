@@ -84,15 +84,17 @@ def test_the_makefile_the_build_and_the_source():
         assert "set_kernel_name" not in text and "set_kernel_variant" not in text, path
         assert "atomic" not in text.lower() and "asm" not in text, path
     includes = re.findall(r'#include\s+[<"]([^>"]+)[>"]', src)
-    assert includes == ["../../include/mbnb_moegemm.h", "host.h", "mx_decode.h", "mx_experts.h"]
+    assert includes == ["../../include/mbnb_moegemm.h", "host.h", "mx_decode.h", "mx_experts.h", "mx_plan.h"]
     assert "mbnb_moegemm_last_launch" in src and "last_launch()" in src
     for kernel in ("k_plan_count", "k_plan_fill", "k_mx_experts_grouped", "k_routed_sum"):
         assert kernel in src, kernel
     shared = open(os.path.join(CSRC, "mx_decode.h")).read()
-    for name in ("decode8_16", "mfma16", "transpose_blocks", "block_scale", "load_bias", "store_out", "lane_rank",
-                 "check_expert_call"):                       # called, not restated (scale_value is reached through block_scale)
+    for name in ("decode8_16", "mfma16", "transpose_blocks", "block_scale", "load_bias", "store_out",
+                 "lane_rank"):                               # called, not restated (scale_value is reached through block_scale)
         assert not re.search(r"^(?:__device__ __forceinline__|static(?: inline)?) [\w ]+ " + name + r"\(", src, flags=re.M), name
         assert re.search(r"\b" + name + r"(?:<\w+>)?\(", src) and name in shared, name
+    # check_expert_call is reached through mx_plan.h's check_grouped_call, which tests/test_moemx_host.py holds
+    assert "check_expert_call(" not in src and "check_grouped_call(what" in src and "check_expert_call(what, 0, 0, K" in open(os.path.join(CSRC, "mx_plan.h")).read()
     for name in ("transpose_blocks", "block_scale"):         # defined once in mx_decode.h, as tests/test_moe_host.py holds for the rest
         assert len(re.findall(r"^__device__ __forceinline__ [\w ]+ " + name + r"\(", shared, flags=re.M)) == 1, name
     # the transpose and the NaN-scale rule are mx_decode.h's text alone
