@@ -35,6 +35,11 @@
  * The launch has ceil(N / MBNB_MOEMX_COL_TILE) x max_tiles workgroups; those past n_tiles leave before they touch a weight byte.
  *
  * Alignment: x_codes, w_codes and plan on 16 bytes; ids on 4; out and bias on their element size; x_scales and w_scales none.
+ *
+ * THE EXPERT MLP on the same kernel: mbnb_moemx_gate_up_glu, then mbnb_moemx_down_sum over its output, with the
+ * conventions, limits and order of checks of mbnb_moemx_experts.  The intermediate exists in memory as MX codes and scale bytes
+ * only: h_codes uint8 [T * A, I] (fp8) or [T * A, I / 2] (fp4) and h_scales uint8 [T * A, I / 32], what mbnb_mx_quantize would
+ * write for the f32 activated rows.
  */
 #ifndef MBNB_MOEMX_H
 #define MBNB_MOEMX_H
@@ -68,7 +73,8 @@ enum { MBNB_MOEMX_OK = 0, MBNB_MOEMX_ERR_ARG = -1, MBNB_MOEMX_ERR_SHAPE = -2, MB
 
 int mbnb_moemx_abi_version(void);
 const char *mbnb_moemx_last_error(void);
-/* e.g. "mx_grouped_scaled fp8 shared E32 P4096 64x256" or "mx_grouped_scaled fp4 slot E9 P300 64x256"; "" before this
+/* e.g. "mx_grouped_scaled fp8 shared E32 P4096 64x256" or "mx_grouped_scaled fp4 slot E9 P300 64x256";
+ * "mx_grouped_scaled_glu fp8>fp8 E32 P4096 64x256"; "mx_grouped_scaled_down_sum fp8 E32 P4096 64x256 A4"; "" before this
  * thread's first launch */
 const char *mbnb_moemx_last_launch(void);
 
@@ -84,6 +90,46 @@ int mbnb_moemx_experts(const void *x_codes, const void *x_scales, int act_elem,
                        const void *w_codes, const void *w_scales, int64_t E, int64_t N,
                        const int32_t *ids, const void *bias, int bias_dtype, void *out, int out_dtype,
                        const void *plan, int64_t plan_bytes, void *stream);
+
+/*
+ * One launch: the gate / up projection with the gated activation and the MX quantiser as its epilogue.  x_codes / x_scales: T
+ * rows of act_elem, shared by a token's slots.  w_codes [E, 2 I, K / 2] and w_scales [E, 2 I, K / 32] with interleaved rows, row
+ * 2 j gate j and row 2 j + 1 up j; bias NULL or [E, 2 I], interleaved the same way.  I % 32 == 0 (else MBNB_MOEMX_ERR_SHAPE): an
+ * activated row is quantised in whole blocks.  With pre[p, n] the f32 value mbnb_moemx_experts writes for out_dtype f32,
+ *   g = min(pre[p, 2 j], limit);  u = clamp(pre[p, 2 j + 1], -limit, limit);  h[p, j] = (u + 1) * (g * (1 / (1 + expf(-(alpha * g)))))
+ * every operation a separate f32 rounding, the operation chain of mbnb_moegemm_gate_up_glu; then the 32 values of every block of
+ * h[p] are quantised by mbnb_mx.h's rule to h_elem: byte = max(E(amax) - emax, 0), a block that holds a NaN or an Inf gets byte
+ * 0xFF and codes 0, elements round to nearest, ties to the even code, saturating, the sign of zero kept.  h_elem must equal
+ * act_elem (MBNB_MOEMX_ERR_ARG otherwise).  alpha finite, limit > 0 (+Inf: no clamp), else MBNB_MOEMX_ERR_ARG.  A pair whose id
+ * is outside [0, E) gets codes 0 and scale bytes 0, the quantised row of +0.0.  Every byte of h_codes and h_scales is written
+ * exactly once.  h_codes on 16 bytes, h_scales none.
+ */
+int mbnb_moemx_gate_up_glu(const void *x_codes, const void *x_scales, int act_elem,
+                           int64_t T, int64_t A, int64_t K,
+                           const void *w_codes, const void *w_scales, int64_t E, int64_t I,
+                           const int32_t *ids, const void *bias, int bias_dtype, float alpha, float limit,
+                           void *h_codes, void *h_scales, int h_elem,
+                           const void *plan, int64_t plan_bytes, void *stream);
+
+/* The bytes of mbnb_moemx_down_sum's workspace for P = T * A pairs: 4 P N rounded up to 256; negative: a status. */
+int64_t mbnb_moemx_workspace_bytes(int64_t P, int64_t N);
+
+/*
+ * Two launches: the down projection and the routed sum.  h_codes / h_scales: a row per pair, T * A rows of act_elem over K.  The
+ * first launch is mbnb_moemx_experts with out_dtype f32 into the workspace y [T * A, N]; the second evaluates, one thread per
+ * four consecutive outputs of a token,
+ *   acc = +0.0;  for a = 0 .. A - 1 in this order, pairs with an id outside [0, E) skipped:  acc = fmaf(rw[t, a], y[t * A + a, n], acc)
+ *   out[t, n] = round(acc)
+ * the formula of mbnb_moegemm_down_sum.  A skipped pair's routing weight and workspace row are not read.  rw [T, A] of rw_dtype
+ * (any of the three), on its element size; out [T, N] of out_dtype.  workspace: 16-byte aligned, at least
+ * mbnb_moemx_workspace_bytes(T * A, N) bytes (else MBNB_MOEMX_ERR_WORKSPACE); its contents are undefined afterwards.
+ */
+int mbnb_moemx_down_sum(const void *h_codes, const void *h_scales, int act_elem,
+                        int64_t T, int64_t A, int64_t K,
+                        const void *w_codes, const void *w_scales, int64_t E, int64_t N,
+                        const int32_t *ids, const void *bias, int bias_dtype, const void *rw, int rw_dtype,
+                        void *out, int out_dtype, void *workspace, int64_t workspace_bytes,
+                        const void *plan, int64_t plan_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ library is missing or a call fails, the caller gets a RuntimeError.
 from __future__ import annotations
 
 import os
-from ctypes import c_char_p, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 from typing import Optional
 
 from . import _loader
@@ -33,6 +33,11 @@ _SIGNATURES = {
     "mbnb_moemx_last_launch": (c_char_p, []),
     "mbnb_moemx_experts": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "mbnb_moemx_gate_up_glu": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "mbnb_moemx_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "mbnb_moemx_down_sum": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -54,6 +59,13 @@ def lib():
 def check(status: int, what: str) -> None:
     if status != 0:
         raise _loader.failed(globals(), status, what)
+
+
+def workspace_bytes(P: int, N: int) -> int:
+    n = lib().mbnb_moemx_workspace_bytes(P, N)
+    if n < 0:
+        check(int(n), "workspace_bytes")
+    return int(n)
 
 
 def last_launch() -> str:

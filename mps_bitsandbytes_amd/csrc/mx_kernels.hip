@@ -43,26 +43,12 @@ using mbnb::mx::dma16;
 using mbnb::mx::fold16;
 using mbnb::mx::scaled_mfma;
 using mbnb::mx::scaled_value;
+using mbnb::mx::enc_e2m1;                  // the element encoders: mx_scaled.h, shared with k_mx_experts_scaled's GluQ epilogue
+using mbnb::mx::enc_e4m3;
 
 constexpr int kThreads = mbnb::mx::kScaledThreads;    // every launch: 4 waves
 
 // ---------------------------------------------------------------- the element formats
-// |a| -> E2M1 code 0..7 (0, .5, 1, 1.5, 2, 3, 4, 6), nearest, ties to the even code, everything above 5 to 6
-__device__ __forceinline__ uint32_t enc_e2m1(float a) {
-    return (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
-           (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
-}
-
-// the bits of |a| (finite) -> E4M3 code 0..0x7E, RNE, saturating at 448
-__device__ __forceinline__ uint32_t enc_e4m3(uint32_t a) {
-    if (a >= 0x3C800000u) {                                  // 2^-6 and up: the normal codes
-        a += 0x7FFFFu + ((a >> 20) & 1u);                    // RNE at mantissa bit 20; a carry moves into the exponent
-        const uint32_t code = (a >> 20) - (120u << 3);       // exponent bias 127 -> 7
-        return code < 0x7Eu ? code : 0x7Eu;
-    }
-    return (uint32_t)rintf(__uint_as_float(a) * 512.0f);     // multiples of 2^-9: 0..8, and 8 is the first normal code
-}
-
 __device__ __forceinline__ float dec_e2m1(uint32_t c) {
     // magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6 as f32 bits: codes 2..7 are (1 + m/2) * 2^(e - 1)
     const uint32_t m = c & 7u;

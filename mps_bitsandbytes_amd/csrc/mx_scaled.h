@@ -4,7 +4,8 @@
 // of a K-step, the 16-byte LDS-DMA, the fold of a ballot to a NaN mask, the call of the scaled MFMA and the epilogue value.  Each kernel
 // keeps its own K loop (the order inside a K-step, the scale path, the edge addressing and the wait differ on purpose), its own
 // store, and -- written out, because as helpers they changed both kernels' instruction streams (§35) -- the fragment reads, the
-// zeros past K and the loop over the ballots; a host test holds those texts equal.  All of it forced inline.
+// zeros past K and the loop over the ballots; a host test holds those texts equal.  All of it forced inline.  At the end, the
+// element encoders of the MX quantiser: k_mx_quantize and the GluQ epilogue of k_mx_experts_scaled share them.
 //
 // The operand map of the instruction: lane l = (g = l >> 4, fr = l & 15) holds row (A) / column (B) fr; fp4: the
 // k block g as 16 bytes; fp8: registers 0..3 the 16 k from 16 g, registers 4..7 the 16 k from 64 + 16 g; scale register byte 0:
@@ -50,6 +51,24 @@ __device__ __forceinline__ float scaled_value(float acc, float b, bool col_nan, 
     float v = acc + b;
     if (col_nan || ((a_nan >> row_bit) & 1u)) v = __uint_as_float(0x7FC00000u);
     return v;
+}
+
+// ---------------------------------------------------------------- the element encoders of the MX quantiser (include/mbnb_mx.h)
+// k_mx_quantize and the GluQ epilogue of k_mx_experts_scaled round an element through these and nothing else.
+// |a| -> E2M1 code 0..7 (0, .5, 1, 1.5, 2, 3, 4, 6), nearest, ties to the even code, everything above 5 to 6
+__device__ __forceinline__ uint32_t enc_e2m1(float a) {
+    return (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+           (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+}
+
+// the bits of |a| (finite) -> E4M3 code 0..0x7E, RNE, saturating at 448
+__device__ __forceinline__ uint32_t enc_e4m3(uint32_t a) {
+    if (a >= 0x3C800000u) {                                  // 2^-6 and up: the normal codes
+        a += 0x7FFFFu + ((a >> 20) & 1u);                    // RNE at mantissa bit 20; a carry moves into the exponent
+        const uint32_t code = (a >> 20) - (120u << 3);       // exponent bias 127 -> 7
+        return code < 0x7Eu ? code : 0x7Eu;
+    }
+    return (uint32_t)rintf(__uint_as_float(a) * 512.0f);     // multiples of 2^-9: 0..8, and 8 is the first normal code
 }
 
 }  // namespace mx

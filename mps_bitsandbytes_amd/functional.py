@@ -2369,6 +2369,174 @@ def matmul_mxfp4_experts_scaled(input: Tensor, weight: Tensor, weight_scales: Te
     return _experts_scaled(what, act, ops, plan)
 
 
+# ----------------------------------------------------------------------------- the expert MLP on the block-scaled MFMA
+# libmbnb_moemx.so: the gate / up launch of k_mx_experts_scaled quantises its gated activation to MX in its
+# epilogue, the down launch reads those codes as they lie, k_scaled_slot_sum adds a token's slots.  Opt-in, like §34's projection.
+def _scaled_act(what: str, act_format) -> Tuple[int, str]:
+    act = _mx_elem(act_format, what)
+    return act, "fp8" if act == _moemx_native.FP8 else "fp4"
+
+
+def _scaled_glu_call(what, act, codes, scales, ids, ops, alpha, limit, q, h_codes, h_scales, stream) -> None:
+    """mbnb_moemx_gate_up_glu over the tokens of one cut: their quantised rows and ids -> h_codes / h_scales [tokens, A, .]"""
+    _, w, s, _, b, _, _, A, E, N, K, _, _ = ops
+    _moemx_native.check(_moemx_native.lib().mbnb_moemx_gate_up_glu(
+        ptr(codes), ptr(scales), act, ids.shape[0], A, K, ptr(w), ptr(s), E, N // 2, ptr(ids), ptr(b),
+        0 if b is None else _native.DTYPE_CODE[b.dtype], alpha, limit, ptr(h_codes), ptr(h_scales), act, ptr(q), q.numel(), stream), what)
+
+
+def _scaled_sum_call(what, act, h_codes, h_scales, ops, t0, t1, q, out, ws, stream) -> None:
+    """mbnb_moemx_down_sum over the tokens [t0, t1): h_codes / h_scales [t1 - t0, A, .] -> out[t0:t1]"""
+    w, s, ids, b, rw, A, E, N, K, ocode = ops
+    _moemx_native.check(_moemx_native.lib().mbnb_moemx_down_sum(
+        ptr(h_codes), ptr(h_scales), act, t1 - t0, A, K, ptr(w), ptr(s), E, N, ptr(ids[t0:t1]), ptr(b),
+        0 if b is None else _native.DTYPE_CODE[b.dtype], ptr(rw[t0:t1]), _native.DTYPE_CODE[rw.dtype], ptr(out[t0:t1]), ocode, ptr(ws), ws.numel(),
+        ptr(q), q.numel(), stream), what)
+
+
+def _scaled_glu_operands(what: str, input, weight, weight_scales, expert_ids, bias, alpha, limit):
+    alpha, limit = _glu_params(what, alpha, limit, weight)
+    if weight.dim() in (3, 4) and (weight.shape[1] // 2) % _moemx_native.BLOCK:
+        raise ValueError(f"{what}: the intermediate size ({weight.shape[1] // 2}) must be a multiple of the MX block, {_moemx_native.BLOCK}: "
+                         "an activated row is quantised in whole blocks")
+    return _expert_operands(what, _moegemm_native, input, weight, weight_scales, expert_ids, bias, False, None), alpha, limit
+
+
+def _scaled_sum_operands(what: str, device, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
+                         bias: Optional[Tensor], out_dtype: torch.dtype):
+    """The checks of the down projection over an MX intermediate on `device` -> ((w, s, ids, b, rw, A, E, N, K, out code), T)"""
+    if weight.dtype != torch.uint8 or weight_scales.dtype != torch.uint8 or weight.dim() not in (3, 4) or weight_scales.dim() != 3:
+        raise ValueError(f"{what}: weight must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16] and weight_scales uint8 [E, N, K / 32]")
+    weight = weight.reshape(weight.shape[0], weight.shape[1], -1)
+    E, N, K = weight.shape[0], weight.shape[1], weight.shape[2] * 2
+    _mx_width(K, what)
+    if not 0 < E <= _moemx_native.MAX_EXPERTS or N <= 0 or tuple(weight_scales.shape) != (E, N, K // _moemx_native.BLOCK):
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} with weight_scales {tuple(weight_scales.shape)}: 1 to {_moemx_native.MAX_EXPERTS} "
+                         f"experts and scales [E, N, K / 32] = {(E, N, K // _moemx_native.BLOCK)}")
+    _check_expert_ids(what, expert_ids)
+    T, A = expert_ids.shape
+    if bias is not None and tuple(bias.shape) != (E, N):
+        raise ValueError(f"{what}: bias {tuple(bias.shape)} does not match [E, N] = {(E, N)}")
+    if tuple(routing_weights.shape) != (T, A) or not routing_weights.dtype.is_floating_point:
+        raise ValueError(f"{what}: routing_weights must be a floating-point tensor [T, A] = {(T, A)}, got {routing_weights.dtype} "
+                         f"{tuple(routing_weights.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (bias, routing_weights)):
+        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its bias or routing weights "
+                                  "(call it under torch.no_grad(), or detach them)")
+    ocode = dtype_code(out_dtype, what)
+    for t in (weight, expert_ids):
+        _check_device(t, what)
+    b = None if bias is None else bias.to(device).contiguous()
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    rw = routing_weights.to(device)
+    rw = (rw if rw.dtype in _native.DTYPE_CODE else rw.float()).contiguous()
+    return (_aligned16(weight), weight_scales.to(device).contiguous(), _int32_ids(expert_ids.to(device)), b, rw, A, E, N, K, ocode), T
+
+
+def matmul_mxfp4_experts_scaled_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
+                                    alpha: float = 1.702, limit: float = 7.0, plan=None, act_format: str = "fp8") -> Tuple[Tensor, Tensor]:
+    """
+    `matmul_mxfp4_experts_grouped_glu` on the block-scaled MFMA with an MX result -> ``(codes, scales)``: `codes`
+    uint8 [T, A, I] (``"fp8"``) or [T, A, I / 2] (``"fp4"``), `scales` uint8 [T, A, I / 32], what ``quantize_mx`` gives the f32
+    gated activation of every pair.  `input` [T, K] is quantised to `act_format` first (T rows, one launch), then one launch of
+    `k_mx_experts_scaled` per cut of `MOE_GROUPED_MAX_PAIRS` pairs computes the projection, the gated activation in f32 (the
+    operation chain of `matmul_mxfp4_experts_glu`) and the quantiser: a wave's 64 interleaved weight rows are one MX block of the
+    result.  I must be a multiple of 32.  A pair whose id is outside [0, E) gets codes 0 and scale bytes 0.  `plan` as in
+    `matmul_mxfp4_experts_grouped`.  Inference only.
+    """
+    what = "matmul_mxfp4_experts_scaled_glu"
+    act, elem = _scaled_act(what, act_format)
+    ops, alpha, limit = _scaled_glu_operands(what, input, weight, weight_scales, expert_ids, bias, alpha, limit)
+    x, ids, T, A, E, I = ops[0], ops[3], ops[6], ops[7], ops[8], ops[9] // 2
+    h_codes = torch.empty(T, A, I if act == _moemx_native.FP8 else I // 2, dtype=torch.uint8, device=x.device)
+    h_scales = torch.empty(T, A, I // _moemx_native.BLOCK, dtype=torch.uint8, device=x.device)
+    if T * A == 0:
+        return h_codes, h_scales
+    plans = _grouped_plans_of(what, plan, ids, T, A, E)
+    codes, scales = quantize_mx(x, elem)
+    with on_device(x.device):
+        stream = stream_ptr(x.device)
+        for (t0, t1), q in zip(_grouped_cuts(T, A), plans):
+            _scaled_glu_call(what, act, codes[t0:t1], scales[t0:t1], ids[t0:t1], ops, alpha, limit, q, h_codes[t0:t1], h_scales[t0:t1], stream)
+    return h_codes, h_scales
+
+
+def matmul_mxfp4_experts_scaled_sum(input, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, routing_weights: Tensor,
+                                    bias: Optional[Tensor] = None, dtype: Optional[torch.dtype] = None, plan=None,
+                                    act_format: str = "fp8") -> Tensor:
+    """
+    `matmul_mxfp4_experts_grouped_sum` on the block-scaled MFMA over an MX intermediate -> ``[T, N]`` of `dtype`
+    (default bfloat16).  `input` is ``(codes, scales)`` of `act_format` as `matmul_mxfp4_experts_scaled_glu` returns them, a row per
+    pair.  Two launches per cut of `MOE_GROUPED_MAX_PAIRS` pairs: `k_mx_experts_scaled` in f32 into a workspace that is a
+    ``torch.empty`` of this call, then `k_scaled_slot_sum`: ``acc = fmaf(rw[t, a], y[t, a, n], acc)`` over the slots in their order
+    from +0.0, a slot whose id is outside [0, E) skipped with its routing weight unread, one rounding.  Inference only.
+    """
+    what = "matmul_mxfp4_experts_scaled_sum"
+    act, _ = _scaled_act(what, act_format)
+    if (not isinstance(input, (tuple, list)) or len(input) != 2
+            or any(not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3 for t in input)):
+        raise ValueError(f"{what}: input must be (codes, scales), two uint8 tensors [T, A, .] as matmul_mxfp4_experts_scaled_glu returns them")
+    _check_device(input[0], what)
+    h_codes, h_scales = _aligned16(input[0]), input[1].to(input[0].device).contiguous()
+    out_dtype = torch.bfloat16 if dtype is None else dtype
+    ops, T = _scaled_sum_operands(what, h_codes.device, weight, weight_scales, expert_ids, routing_weights, bias, out_dtype)
+    ids, A, E, N, K = ops[2], ops[5], ops[6], ops[7], ops[8]
+    want = ((T, A, K if act == _moemx_native.FP8 else K // 2), (T, A, K // _moemx_native.BLOCK))
+    if (tuple(h_codes.shape), tuple(h_scales.shape)) != want:
+        raise ValueError(f"{what}: codes {tuple(h_codes.shape)} and scales {tuple(h_scales.shape)} do not match expert_ids "
+                         f"{tuple(expert_ids.shape)} and K = {K}: expected {want[0]} and {want[1]}")
+    if T * A == 0:
+        return torch.zeros(T, N, dtype=out_dtype, device=h_codes.device)
+    out = torch.empty(T, N, dtype=out_dtype, device=h_codes.device)
+    plans, cuts = _grouped_plans_of(what, plan, ids, T, A, E), _grouped_cuts(T, A)
+    ws = torch.empty(_moemx_native.workspace_bytes((cuts[0][1] - cuts[0][0]) * A, N), dtype=torch.uint8, device=out.device)
+    with on_device(out.device):
+        stream = stream_ptr(out.device)
+        for (t0, t1), q in zip(cuts, plans):
+            _scaled_sum_call(what, act, h_codes[t0:t1], h_scales[t0:t1], ops, t0, t1, q, out, ws, stream)
+    return out
+
+
+def moe_mlp_mxfp4_scaled(input: Tensor, gate_up_weight: Tensor, gate_up_scales: Tensor, gate_up_bias: Optional[Tensor], down_weight: Tensor,
+                         down_scales: Tensor, down_bias: Optional[Tensor], expert_ids: Tensor, routing_weights: Tensor, alpha: float = 1.702,
+                         limit: float = 7.0, dtype: Optional[torch.dtype] = None, act_format: str = "fp8") -> Tensor:
+    """
+    `moe_mlp_mxfp4` on the block-scaled MFMA -> ``[T, H']`` of `dtype` (default: the input's): the bits of
+    ``matmul_mxfp4_experts_scaled_sum(matmul_mxfp4_experts_scaled_glu(input, gate_up...), down...)``.  Per cut of
+    `MOE_GROUPED_MAX_PAIRS` pairs: one plan of the routing, the quantiser over the cut's token rows, the gate / up launch with the
+    gated activation and the MX quantiser as its epilogue, the down launch and the sum over the slots: four launches beside the
+    plan's two, no torch op between them and nothing synchronised, so the call can be captured in a graph.  The intermediate
+    exists as MX codes and scale bytes only, in one buffer that every cut reuses.  Opt-in: the result differs from
+    `moe_mlp_mxfp4`'s by the quantisation of both activations (DESIGN.md §36 has the measured error).
+    """
+    what = "moe_mlp_mxfp4_scaled"
+    act, elem = _scaled_act(what, act_format)
+    up, alpha, limit = _scaled_glu_operands(what, input, gate_up_weight, gate_up_scales, expert_ids, gate_up_bias, alpha, limit)
+    x, ids, T, A, E, I = up[0], up[3], up[6], up[7], up[8], up[9] // 2
+    out_dtype = input.dtype if dtype is None else dtype
+    down, _ = _scaled_sum_operands(what, x.device, down_weight, down_scales, ids, routing_weights, down_bias, out_dtype)
+    N = down[7]
+    if down[6] != E or down[8] != I:
+        raise ValueError(f"{what}: down_weight has {down[6]} experts over K = {down[8]}, gate_up_weight {E} experts and an intermediate size of {I}")
+    if T * A == 0:
+        return torch.zeros(T, N, dtype=out_dtype, device=x.device)
+    out = torch.empty(T, N, dtype=out_dtype, device=x.device)
+    cuts = _grouped_cuts(T, A)
+    step = cuts[0][1] - cuts[0][0]                           # the first cut is the largest: its buffers serve them all
+    h_codes = torch.empty(step, A, I if act == _moemx_native.FP8 else I // 2, dtype=torch.uint8, device=x.device)
+    h_scales = torch.empty(step, A, I // _moemx_native.BLOCK, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(_moemx_native.workspace_bytes(step * A, N), dtype=torch.uint8, device=x.device)
+    plans = _grouped_plans(what, ids, T, A, E)
+    for (t0, t1), q in zip(cuts, plans):
+        codes, scales = quantize_mx(x[t0:t1], elem)
+        with on_device(x.device):
+            stream = stream_ptr(x.device)
+            _scaled_glu_call(what, act, codes, scales, ids[t0:t1], up, alpha, limit, q, h_codes, h_scales, stream)
+            _scaled_sum_call(what, act, h_codes, h_scales, down, t0, t1, q, out, ws, stream)
+    return out
+
+
 def matmul_mxfp4_experts_grouped_glu(input: Tensor, weight: Tensor, weight_scales: Tensor, expert_ids: Tensor, bias: Optional[Tensor] = None,
                                      alpha: float = 1.702, limit: float = 7.0, dtype: Optional[torch.dtype] = None, plan=None) -> Tensor:
     """

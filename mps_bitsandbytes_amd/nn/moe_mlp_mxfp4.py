@@ -6,7 +6,8 @@ it is: `gate_up_proj_blocks` uint8 [E, 2I, H / 32, 16] with interleaved rows (ro
 `gate_up_proj_scales` uint8 [E, 2I, H / 32], `gate_up_proj_bias` [E, 2I], `down_proj_blocks` uint8 [E, H, I / 32, 16],
 `down_proj_scales` uint8 [E, H, I / 32], `down_proj_bias` [E, H].  The forward is `functional.moe_mlp_mxfp4`: three launches, the
 gated activation an epilogue of the gate / up launch, the routed sum over the slots on the device.  The router
-stays the caller's.  Inference only.
+stays the caller's.  Inference only.  With the class attribute `act_format` set to "fp8" / "fp4" (on the class or on a module) the
+forward is `functional.moe_mlp_mxfp4_scaled`: both projections on the block-scaled MFMA, the intermediate in MX only.
 """
 from typing import Optional
 
@@ -21,6 +22,7 @@ _BLOCK = 32
 
 class MoEMLPMXFP4(QuantizedModule):
     _anchor = 'gate_up_proj_blocks'
+    act_format = "none"        # "fp8" / "fp4": assigned on the class or on a module; both activations are then quantised to MX
 
     def __init__(self, num_experts: int, hidden_size: int, intermediate_size: int, bias: bool = True, alpha: float = 1.702,
                  limit: float = 7.0, device=None, compute_dtype: torch.dtype = torch.bfloat16):
@@ -43,6 +45,12 @@ class MoEMLPMXFP4(QuantizedModule):
 
     def forward(self, x: Tensor, expert_ids: Tensor, routing_weights: Tensor) -> Tensor:
         """x [T, H], f16 / bf16; expert_ids and routing_weights [T, A] -> [T, H] in x's dtype."""
+        if self.act_format != "none":
+            if self.act_format not in ("fp8", "fp4"):
+                raise ValueError(f"MoEMLPMXFP4: unknown act_format {self.act_format!r} (supported: 'none', 'fp8', 'fp4')")
+            return F.moe_mlp_mxfp4_scaled(x, self.gate_up_proj_blocks, self.gate_up_proj_scales, self.gate_up_proj_bias, self.down_proj_blocks,
+                                          self.down_proj_scales, self.down_proj_bias, expert_ids, routing_weights, self.alpha, self.limit,
+                                          act_format=self.act_format)
         return F.moe_mlp_mxfp4(x, self.gate_up_proj_blocks, self.gate_up_proj_scales, self.gate_up_proj_bias, self.down_proj_blocks,
                                self.down_proj_scales, self.down_proj_bias, expert_ids, routing_weights, self.alpha, self.limit)
 
