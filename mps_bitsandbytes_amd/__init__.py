@@ -29,6 +29,7 @@ from .functional import (
     moe_router_topk, moe_block_mxfp4,
     matmul_mxfp4_experts_grouped, matmul_mxfp4_experts_scaled, matmul_mxfp4_experts_scaled_glu, matmul_mxfp4_experts_scaled_sum, moe_mlp_mxfp4_scaled,
     matmul_mxfp4_experts_grouped_glu, matmul_mxfp4_experts_grouped_sum, moe_grouped_plan,
+    quantize_fp8_rows, matmul_fp8_w8a8, linear_fp8_w8a8,
 )
 from .nn import (Linear4bit, Linear4bitGroup, Linear4bitLoRA, Linear4bitLoRAGroup, Linear8bit, LinearFP8, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
                  OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup, LinearMXFP4, ExpertsMXFP4, MoEMLPMXFP4, MoERouterTopK, MoEBlockMXFP4)
@@ -76,4 +77,5 @@ __all__ = [
     'moe_router_topk', 'MoERouterTopK', 'moe_block_mxfp4', 'MoEBlockMXFP4',
     'matmul_mxfp4_experts_grouped', 'matmul_mxfp4_experts_scaled', 'matmul_mxfp4_experts_scaled_glu', 'matmul_mxfp4_experts_scaled_sum', 'moe_mlp_mxfp4_scaled',
     'matmul_mxfp4_experts_grouped_glu', 'matmul_mxfp4_experts_grouped_sum', 'moe_grouped_plan',
+    'quantize_fp8_rows', 'matmul_fp8_w8a8', 'linear_fp8_w8a8',
 ]

@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
+from . import _batch_native, _fp8_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -1129,6 +1129,121 @@ def matmul_fp8_e4m3(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: 
     with on_device(x2.device):
         check(_native.lib().mbnb_linear_fp8(ptr(x2), dcode, M, K, ptr(w), ptr(s), N, ptr(b), ptr(out), ptr(ws), ws_bytes,
                                             flags, stream_ptr(x2.device)), "matmul_fp8_e4m3")
+    out = out.reshape(*lead, N)
+    return out.squeeze(0) if is_1d else out
+
+
+# ============================================================================= W8A8 FP8: both operands E4M3, on the FP8 MFMA
+# No counterpart in the reference.  The weight is a LinearFP8 buffer as it lies in memory (the reference's decoder is OCP E4M3);
+# the activation rows are quantised by a rule of their own (include/mbnb_fp8.h), which maps a row's maximum to
+# 448 and saturates nothing below it.  Opt-in: nothing takes this route unless it is called.  Inference only.
+def _fp8_width(K: int, what: str) -> None:
+    if K <= 0 or K % _fp8_native.WIDTH:
+        raise ValueError(f"{what}: the last dimension ({K}) must be a positive multiple of {_fp8_native.WIDTH}")
+
+
+def _fp8_no_grad(what: str, *tensors: Optional[Tensor]) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"{what} is inference-only: it defines no gradient for its input or bias "
+                                  "(call it under torch.no_grad(), or detach them)")
+
+
+def _fp8_weight(what: str, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor], device):
+    """the checked operands of the weight side: (w uint8 [N, K] on 16 bytes, sW f32 [N], bias or None, its dtype code)"""
+    _check_device(weight, what)
+    if weight.dim() != 2 or weight.dtype != torch.uint8:
+        raise ValueError(f"{what}: weight must be a 2D uint8 tensor of E4M3 codes")
+    N, K = weight.shape
+    _fp8_width(K, what)
+    if weight_scales.dim() != 1 or weight_scales.shape[0] != N:
+        raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: expected {(N,)}")
+    b = None if bias is None else bias.to(device).contiguous()
+    if b is not None and (b.dim() != 1 or b.shape[0] != N):
+        raise ValueError(f"{what}: bias {tuple(b.shape)} does not match N = {N}")
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    return _aligned16(weight), weight_scales.to(device=device, dtype=torch.float32).contiguous(), b, 0 if b is None else _native.DTYPE_CODE[b.dtype]
+
+
+def quantize_fp8_rows(tensor: Tensor) -> Tuple[Tensor, Tensor]:
+    """
+    Quantise the rows of a 2-D tensor [M, K] (K % 16 == 0) to OCP E4M3 with one f32 scale per row: returns (uint8 [M, K],
+    f32 [M]) with scale = max|row| / 448 and code = E4M3(x * (448 / max|row|)), round to nearest even.  Unlike quantize_fp8_e4m3
+    (the reference's encoder, which saturates everything from 256 up to 240) the row's maximum maps to 448 and nothing is clipped.
+    An all-zero row has scale 0; a row that holds an Inf or a NaN has scale NaN and codes 0.
+    """
+    _check_device(tensor, "quantize_fp8_rows")
+    if tensor.dim() != 2:
+        raise ValueError("quantize_fp8_rows: input must be 2D")
+    M, K = tensor.shape
+    _fp8_width(K, "quantize_fp8_rows")
+    x = _aligned16(tensor if tensor.dtype in _native.DTYPE_CODE else tensor.float())
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(M, dtype=torch.float32, device=x.device)
+    with on_device(x.device):
+        _fp8_native.check(_fp8_native.lib().mbnb_fp8_quantize_rows(ptr(x), dtype_code(x.dtype, "quantize_fp8_rows"), M, K, ptr(q), ptr(scales),
+                                                                   stream_ptr(x.device)), "quantize_fp8_rows")
+    return q, scales
+
+
+def matmul_fp8_w8a8(A: Tensor, A_scales: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None,
+                    dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """
+    ``(dec(A) @ dec(weight)^T) * A_scales[:, None] * weight_scales[None, :] + bias`` over two E4M3 operands (`A` uint8 [M, K],
+    `weight` uint8 [N, K], the scales f32 per row) in one launch on the FP8 MFMA: the counterpart of matmul_int8.  f32
+    accumulation, each scale one f32 product, the bias added in f32, one rounding to `dtype`.
+    """
+    what = "matmul_fp8_w8a8"
+    _fp8_no_grad(what, bias)
+    _check_device(A, what)
+    if A.dim() != 2 or A.dtype != torch.uint8:
+        raise ValueError(f"{what}: A must be a 2D uint8 tensor of E4M3 codes")
+    ocode = dtype_code(dtype, what)
+    w, sw, b, bcode = _fp8_weight(what, weight, weight_scales, bias, A.device)
+    M, K = A.shape
+    N = w.shape[0]
+    if K != w.shape[1]:
+        raise ValueError(f"{what}: A width {K} does not match weight {tuple(weight.shape)}")
+    if A_scales.dim() != 1 or A_scales.shape[0] != M:
+        raise ValueError(f"{what}: A_scales {tuple(A_scales.shape)} do not match A {tuple(A.shape)}: expected {(M,)}")
+    a = _aligned16(A)
+    sa = A_scales.to(device=a.device, dtype=torch.float32).contiguous()
+    out = torch.empty(M, N, dtype=dtype, device=a.device)
+    if M > 0:
+        with on_device(a.device):
+            _fp8_native.check(_fp8_native.lib().mbnb_fp8_matmul(ptr(a), ptr(sa), M, K, ptr(w), ptr(sw), N, ptr(b), bcode, ptr(out), ocode,
+                                                                stream_ptr(a.device)), what)
+    return out
+
+
+def linear_fp8_w8a8(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None,
+                    dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    ``matmul_fp8_w8a8(*quantize_fp8_rows(input[..., K]), weight, weight_scales, bias, dtype)`` as one C call (two launches: the row
+    quantiser into a workspace, then the GEMM), with the bits of the two calls.  `dtype` defaults to the input's.
+    """
+    what = "linear_fp8_w8a8"
+    _fp8_no_grad(what, input, bias)
+    _check_device(input, what)
+    out_dtype = input.dtype if dtype is None else dtype
+    ocode = dtype_code(out_dtype, what)
+    w, sw, b, bcode = _fp8_weight(what, weight, weight_scales, bias, input.device)
+    N, K = w.shape
+    is_1d = input.dim() == 1
+    x = input.unsqueeze(0) if is_1d else input
+    if x.shape[-1] != K:
+        raise ValueError(f"{what}: input width {x.shape[-1]} does not match weight {tuple(weight.shape)}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    x2 = _aligned16(x2 if x2.dtype in _native.DTYPE_CODE else x2.float())
+    M = x2.shape[0]
+    out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
+    if M > 0:
+        ws_bytes = _fp8_native.workspace_bytes(M, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x2.device)
+        with on_device(x2.device):
+            _fp8_native.check(_fp8_native.lib().mbnb_fp8_linear(ptr(x2), dtype_code(x2.dtype, what), M, K, ptr(w), ptr(sw), N, ptr(b), bcode,
+                                                                ptr(out), ocode, ptr(ws), ws_bytes, stream_ptr(x2.device)), what)
     out = out.reshape(*lead, N)
     return out.squeeze(0) if is_1d else out
 

@@ -4,6 +4,9 @@ LinearFP8 — FP8 E4M3 (the reference's format) row-wise quantized linear layer 
 Public surface of the reference module (mps_bitsandbytes/nn/linear_fp8.py:17-168): buffers `weight_fp8` [N, K] uint8 and
 `weight_scales` [N] f32, `bias` Parameter, `from_linear`, `dequantize`.  The forward is `functional.matmul_fp8_e4m3`:
 the W8A16 GEMM kernels with the FP8 byte decoder in the weight producer.
+
+`act_format` (a class attribute, "none" by default) selects what becomes of the activation: "fp8" quantises its rows to E4M3 and
+runs `functional.linear_fp8_w8a8` over the module's own buffers, both operands on the FP8 MFMA (inference only).
 """
 from typing import Optional
 
@@ -16,6 +19,7 @@ from ._base import QuantizedModule, compute_dtype_for, source_device
 
 class LinearFP8(QuantizedModule):
     _anchor = 'weight_fp8'
+    act_format = "none"        # "fp8": the W8A8 forward over the same buffers; set on the class or on an instance
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None,
                  compute_dtype: torch.dtype = torch.float16):
@@ -26,6 +30,8 @@ class LinearFP8(QuantizedModule):
         self._init_bias(bias, device)
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.act_format == "fp8":
+            return F.linear_fp8_w8a8(x, self.weight_fp8, self.weight_scales, self.bias, self.compute_dtype)
         return F.matmul_fp8_e4m3(x, self.weight_fp8, self.weight_scales, self.bias, self.compute_dtype)
 
     @classmethod
