@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _fp8_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
+from . import _batch_native, _fp8_native, _fp8blk_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -1244,6 +1244,128 @@ def linear_fp8_w8a8(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: 
         with on_device(x2.device):
             _fp8_native.check(_fp8_native.lib().mbnb_fp8_linear(ptr(x2), dtype_code(x2.dtype, what), M, K, ptr(w), ptr(sw), N, ptr(b), bcode,
                                                                 ptr(out), ocode, ptr(ws), ws_bytes, stream_ptr(x2.device)), what)
+    out = out.reshape(*lead, N)
+    return out.squeeze(0) if is_1d else out
+
+
+# ============================================================================= block-scaled FP8: 128 x 128 weight blocks, 1 x 128 groups
+# The FP8 checkpoint layout of DeepSeek-V3 / R1 and the Qwen3 -FP8 releases (include/mbnb_fp8blk.h): `weight` E4M3
+# [N, K] with `weight_scale_inv` f32 [ceil(N / 128), ceil(K / 128)], the activation quantised per row and 128-wide k group.  Opt-in,
+# inference only, a library of its own.
+def _fp8_block_weight(what: str, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor], device):
+    """the checked operands of the weight side: (w uint8 [N, K] on 16 bytes, sW f32 [NB, KB], bias or None, its dtype code)"""
+    _check_device(weight, what)
+    if weight.dtype == torch.float8_e4m3fn:
+        weight = weight.view(torch.uint8)
+    if weight.dim() != 2 or weight.dtype != torch.uint8:
+        raise ValueError(f"{what}: weight must be a 2D uint8 (or float8_e4m3fn) tensor of E4M3 codes")
+    N, K = weight.shape
+    _fp8_width(K, what)
+    want = (_fp8blk_native.blocks(N), _fp8blk_native.blocks(K))
+    if tuple(weight_scales.shape) != want:
+        raise ValueError(f"{what}: weight_scales {tuple(weight_scales.shape)} do not match weight {tuple(weight.shape)}: expected {want}")
+    b = None if bias is None else bias.to(device).contiguous()
+    if b is not None and (b.dim() != 1 or b.shape[0] != N):
+        raise ValueError(f"{what}: bias {tuple(b.shape)} does not match N = {N}")
+    if b is not None and b.dtype not in _native.DTYPE_CODE:
+        b = b.float()
+    return _aligned16(weight), weight_scales.to(device=device, dtype=torch.float32).contiguous(), b, 0 if b is None else _native.DTYPE_CODE[b.dtype]
+
+
+def _quantize_fp8_block(what: str, entry: str, tensor: Tensor, scale_rows: int) -> Tuple[Tensor, Tensor]:
+    _check_device(tensor, what)
+    if tensor.dim() != 2:
+        raise ValueError(f"{what}: input must be 2D")
+    R, K = tensor.shape
+    _fp8_width(K, what)
+    x = _aligned16(tensor if tensor.dtype in _native.DTYPE_CODE else tensor.float())
+    q = torch.empty(R, K, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(scale_rows, _fp8blk_native.blocks(K), dtype=torch.float32, device=x.device)
+    if R > 0:
+        with on_device(x.device):
+            _fp8blk_native.check(getattr(_fp8blk_native.lib(), entry)(ptr(x), dtype_code(x.dtype, what), R, K, ptr(q), ptr(scales),
+                                                                       stream_ptr(x.device)), what)
+    return q, scales
+
+
+def quantize_fp8_groups(tensor: Tensor) -> Tuple[Tensor, Tensor]:
+    """
+    Quantise a 2-D tensor [M, K] (K % 16 == 0) to OCP E4M3 with one f32 scale per row and 128-wide k group: returns (uint8 [M, K],
+    f32 [M, ceil(K / 128)]).  `quantize_fp8_rows`' rule on each group: scale = max|group| / 448, code = E4M3(x * (448 / max|group|)),
+    round to nearest even; an all-zero group has scale 0, a group that holds an Inf or a NaN has scale NaN and codes 0.
+    """
+    return _quantize_fp8_block("quantize_fp8_groups", "mbnb_fp8blk_quantize_groups", tensor, tensor.shape[0] if tensor.dim() == 2 else 0)
+
+
+def quantize_fp8_blocks(tensor: Tensor) -> Tuple[Tensor, Tensor]:
+    """
+    Quantise a weight [N, K] (K % 16 == 0) to OCP E4M3 with one f32 scale per 128 x 128 block: returns (uint8 [N, K],
+    f32 [ceil(N / 128), ceil(K / 128)]), the `weight` and `weight_scale_inv` of a block-scaled FP8 checkpoint.  The rule of
+    `quantize_fp8_groups` on each block; the last block row and column may be partial.
+    """
+    return _quantize_fp8_block("quantize_fp8_blocks", "mbnb_fp8blk_quantize_blocks", tensor,
+                               _fp8blk_native.blocks(tensor.shape[0]) if tensor.dim() == 2 else 0)
+
+
+def matmul_fp8_block(A: Tensor, A_scales: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None,
+                     dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """
+    ``sum_t (A_scales[:, t, None] * weight_scales[n // 128, t]) * (dec(A_t) @ dec(weight_t)^T) + bias`` over two E4M3 operands (`A`
+    uint8 [M, K] with f32 [M, KB] scales, `weight` uint8 or float8_e4m3fn [N, K] with f32 [NB, KB] scales) in one launch on the FP8
+    MFMA: each 128-k block is summed on its own and folded into the f32 sum with its scale product, in ascending order; the bias is
+    added in f32, one rounding to `dtype`.
+    """
+    what = "matmul_fp8_block"
+    _fp8_no_grad(what, bias)
+    _check_device(A, what)
+    if A.dim() != 2 or A.dtype != torch.uint8:
+        raise ValueError(f"{what}: A must be a 2D uint8 tensor of E4M3 codes")
+    ocode = dtype_code(dtype, what)
+    w, sw, b, bcode = _fp8_block_weight(what, weight, weight_scales, bias, A.device)
+    M, K = A.shape
+    N = w.shape[0]
+    if K != w.shape[1]:
+        raise ValueError(f"{what}: A width {K} does not match weight {tuple(weight.shape)}")
+    if tuple(A_scales.shape) != (M, sw.shape[1]):
+        raise ValueError(f"{what}: A_scales {tuple(A_scales.shape)} do not match A {tuple(A.shape)}: expected {(M, sw.shape[1])}")
+    a = _aligned16(A)
+    sa = A_scales.to(device=a.device, dtype=torch.float32).contiguous()
+    out = torch.empty(M, N, dtype=dtype, device=a.device)
+    if M > 0:
+        with on_device(a.device):
+            _fp8blk_native.check(_fp8blk_native.lib().mbnb_fp8blk_matmul(ptr(a), ptr(sa), M, K, ptr(w), ptr(sw), N, ptr(b), bcode, ptr(out),
+                                                                         ocode, stream_ptr(a.device)), what)
+    return out
+
+
+def linear_fp8_block(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None,
+                     dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    ``matmul_fp8_block(*quantize_fp8_groups(input[..., K]), weight, weight_scales, bias, dtype)`` as one C call (two launches: the
+    group quantiser into a workspace, then the GEMM), with the bits of the two calls.  `dtype` defaults to the input's.
+    """
+    what = "linear_fp8_block"
+    _fp8_no_grad(what, input, bias)
+    _check_device(input, what)
+    out_dtype = input.dtype if dtype is None else dtype
+    ocode = dtype_code(out_dtype, what)
+    w, sw, b, bcode = _fp8_block_weight(what, weight, weight_scales, bias, input.device)
+    N, K = w.shape
+    is_1d = input.dim() == 1
+    x = input.unsqueeze(0) if is_1d else input
+    if x.shape[-1] != K:
+        raise ValueError(f"{what}: input width {x.shape[-1]} does not match weight {tuple(weight.shape)}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    x2 = _aligned16(x2 if x2.dtype in _native.DTYPE_CODE else x2.float())
+    M = x2.shape[0]
+    out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
+    if M > 0:
+        ws_bytes = _fp8blk_native.workspace_bytes(M, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x2.device)
+        with on_device(x2.device):
+            _fp8blk_native.check(_fp8blk_native.lib().mbnb_fp8blk_linear(ptr(x2), dtype_code(x2.dtype, what), M, K, ptr(w), ptr(sw), N, ptr(b),
+                                                                         bcode, ptr(out), ocode, ptr(ws), ws_bytes, stream_ptr(x2.device)), what)
     out = out.reshape(*lead, N)
     return out.squeeze(0) if is_1d else out
 

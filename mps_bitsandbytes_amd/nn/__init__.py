@@ -21,6 +21,7 @@ from .linear4bit_lora import Linear4bitLoRA, Linear4bitLoRAGroup
 from .linear4bit_multilora import Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup
 from .linear8bit import Linear8bit
 from .linear_fp8 import LinearFP8
+from .linear_fp8_block import LinearFP8Block
 from .linear_mxfp4 import LinearMXFP4
 from .experts_mxfp4 import ExpertsMXFP4
 from .moe_mlp_mxfp4 import MoEMLPMXFP4
@@ -28,6 +29,6 @@ from .moe_block_mxfp4 import MoEBlockMXFP4, MoERouterTopK
 from .outlier_aware import OutlierAwareLinear
 from .switchback import SwitchBackLinear, SwitchBackLinearCallback
 
-__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'LinearMXFP4', 'ExpertsMXFP4', 'MoEMLPMXFP4', 'MoERouterTopK', 'MoEBlockMXFP4', 'OutlierAwareLinear',
+__all__ = sorted(['Linear4bit', 'Linear4bitGroup', 'Linear4bitLoRA', 'Linear4bitLoRAGroup', 'Linear4bitMultiLoRA', 'Linear4bitMultiLoRAGroup', 'Params4bit', 'Linear8bit', 'LinearFP8', 'LinearFP8Block', 'LinearMXFP4', 'ExpertsMXFP4', 'MoEMLPMXFP4', 'MoERouterTopK', 'MoEBlockMXFP4', 'OutlierAwareLinear',
                   'Embedding4bit', 'Embedding8bit', 'EmbeddingNF4', 'EmbeddingFP4',
                   'SwitchBackLinear', 'SwitchBackLinearCallback'])
