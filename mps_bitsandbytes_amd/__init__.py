@@ -30,7 +30,7 @@ from .functional import (
     matmul_mxfp4_experts_grouped, matmul_mxfp4_experts_scaled, matmul_mxfp4_experts_scaled_glu, matmul_mxfp4_experts_scaled_sum, moe_mlp_mxfp4_scaled,
     matmul_mxfp4_experts_grouped_glu, matmul_mxfp4_experts_grouped_sum, moe_grouped_plan,
     quantize_fp8_rows, matmul_fp8_w8a8, linear_fp8_w8a8,
-    quantize_fp8_groups, quantize_fp8_blocks, matmul_fp8_block, linear_fp8_block,
+    quantize_fp8_groups, quantize_fp8_blocks, matmul_fp8_block, linear_fp8_block, linear_fp8_block_weight_only,
 )
 from .nn import (Linear4bit, Linear4bitGroup, Linear4bitLoRA, Linear4bitLoRAGroup, Linear8bit, LinearFP8, LinearFP8Block, Params4bit, Embedding4bit, Embedding8bit, EmbeddingNF4, EmbeddingFP4,
                  OutlierAwareLinear, SwitchBackLinear, SwitchBackLinearCallback, Linear4bitMultiLoRA, Linear4bitMultiLoRAGroup, LinearMXFP4, ExpertsMXFP4, MoEMLPMXFP4, MoERouterTopK, MoEBlockMXFP4)
@@ -79,5 +79,5 @@ __all__ = [
     'matmul_mxfp4_experts_grouped', 'matmul_mxfp4_experts_scaled', 'matmul_mxfp4_experts_scaled_glu', 'matmul_mxfp4_experts_scaled_sum', 'moe_mlp_mxfp4_scaled',
     'matmul_mxfp4_experts_grouped_glu', 'matmul_mxfp4_experts_grouped_sum', 'moe_grouped_plan',
     'quantize_fp8_rows', 'matmul_fp8_w8a8', 'linear_fp8_w8a8',
-    'quantize_fp8_groups', 'quantize_fp8_blocks', 'matmul_fp8_block', 'linear_fp8_block', 'LinearFP8Block',
+    'quantize_fp8_groups', 'quantize_fp8_blocks', 'matmul_fp8_block', 'linear_fp8_block', 'linear_fp8_block_weight_only', 'LinearFP8Block',
 ]

@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import _batch_native, _fp8_native, _fp8blk_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
+from . import _batch_native, _fp8_native, _fp8blk_native, _fp8dec_native, _group_native, _lora_native, _mlora_native, _moe_native, _moegemm_native, _moemlp_native, _moemx_native, _mx_native, _native, _router_native, _sparse_native, _train_native
 from ._native import AbsmaxDesc, check, dtype_code, ptr, stream_ptr, on_device
 
 # ============================================================================= codebooks
@@ -1366,6 +1366,39 @@ def linear_fp8_block(input: Tensor, weight: Tensor, weight_scales: Tensor, bias:
         with on_device(x2.device):
             _fp8blk_native.check(_fp8blk_native.lib().mbnb_fp8blk_linear(ptr(x2), dtype_code(x2.dtype, what), M, K, ptr(w), ptr(sw), N, ptr(b),
                                                                          bcode, ptr(out), ocode, ptr(ws), ws_bytes, stream_ptr(x2.device)), what)
+    out = out.reshape(*lead, N)
+    return out.squeeze(0) if is_1d else out
+
+
+def linear_fp8_block_weight_only(input: Tensor, weight: Tensor, weight_scales: Tensor, bias: Optional[Tensor] = None,
+                                 dtype: Optional[torch.dtype] = None) -> Tensor:
+    """
+    ``input[..., K] @ (dec(weight) * weight_scales per 128 x 128 block)^T + bias`` over the operands of `linear_fp8_block`, for the 1 to
+    16 rows of a token-generation step (include/mbnb_fp8dec.h): ONE launch, the input is NOT quantised and stays in
+    its own dtype, no workspace; the E4M3 weight is streamed once and decoded in registers.  Every 128-k block is summed in f32 and
+    folded into the f32 sum with its block's scale, the bias is added in f32, one rounding to `dtype` (default: the input's).  More
+    rows run as further row chunks of the same launch; every row count goes to the library.
+    """
+    what = "linear_fp8_block_weight_only"
+    _fp8_no_grad(what, input, bias)
+    _check_device(input, what)
+    out_dtype = input.dtype if dtype is None else dtype
+    ocode = dtype_code(out_dtype, what)
+    w, sw, b, bcode = _fp8_block_weight(what, weight, weight_scales, bias, input.device)
+    N, K = w.shape
+    is_1d = input.dim() == 1
+    x = input.unsqueeze(0) if is_1d else input
+    if x.shape[-1] != K:
+        raise ValueError(f"{what}: input width {x.shape[-1]} does not match weight {tuple(weight.shape)}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    x2 = _aligned16(x2 if x2.dtype in _native.DTYPE_CODE else x2.float())
+    M = x2.shape[0]
+    out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
+    if M > 0:
+        with on_device(x2.device):
+            _fp8dec_native.check(_fp8dec_native.lib().mbnb_fp8dec_linear_weight_only(ptr(x2), dtype_code(x2.dtype, what), M, K, ptr(w), ptr(sw), N,
+                                                                                     ptr(b), bcode, ptr(out), ocode, stream_ptr(x2.device)), what)
     out = out.reshape(*lead, N)
     return out.squeeze(0) if is_1d else out
 

@@ -5,6 +5,10 @@ Buffers under the checkpoint's own keys: `weight` [N, K] uint8 (E4M3 codes; a fl
 viewed as uint8 on load), `weight_scale_inv` f32 [ceil(N / 128), ceil(K / 128)] and an optional `bias`.  The forward is
 `functional.linear_fp8_block`: the activation quantised per row and 128-wide k group, both operands on the FP8 MFMA, every
 128-k block folded into the f32 sum with its own scale product.  Inference only.
+
+`act_format` (a class attribute, "fp8" by default: that forward) selects what becomes of the activation: "none" leaves it in its own
+dtype and runs `functional.linear_fp8_block_weight_only` over the same buffers, the one-launch form for the 1 to 16 rows of a
+token-generation step.
 """
 import torch
 from torch import nn, Tensor
@@ -17,6 +21,7 @@ _BLOCK = 128
 
 class LinearFP8Block(QuantizedModule):
     _anchor = 'weight'
+    act_format = "fp8"         # "none": the weight-only decode forward over the same buffers; set on the class or on an instance
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False, device=None, compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
@@ -32,6 +37,10 @@ class LinearFP8Block(QuantizedModule):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.act_format == "none":
+            return F.linear_fp8_block_weight_only(x, self.weight, self.weight_scale_inv, self.bias)
+        if self.act_format != "fp8":
+            raise ValueError(f"LinearFP8Block: unknown act_format {self.act_format!r} (supported: 'fp8', 'none')")
         return F.linear_fp8_block(x, self.weight, self.weight_scale_inv, self.bias)
 
     @classmethod
